@@ -1,6 +1,14 @@
 """Throughput benchmark of the MI355X basketball step (BASELINE.json metric).
 
 python bench.py [--gpus N] [--steps K] [--warmup W] [--worlds 65536] [--agents 2]
+                [--dump-outputs DIR] [--full]
+A plain run sets up, warms up, times the K steps and prints the result line
+(metric, value, unit, ms_per_step, ...).  --full adds everything else the
+line can carry, each a run of its own: the CPU baselines, the per-call and
+end-to-end legs, the events-timed kernel passes behind `roofline`, and the
+other BASELINE configs (the --no-* options subtract from --full).
+--dump-outputs DIR writes what the timed steps left for their caller, after
+the last timed step, as DIR/<name>.npy (see dump_outputs).
 Multi-GPU: python bench.py --gpus N starts N ranks itself (one process per
 GPU); under a launcher (python -m torch.distributed.run --nproc-per-node N ...
 bench.py --gpus N) --gpus must equal WORLD_SIZE.
@@ -27,6 +35,8 @@ sys.path.insert(0, ROOT)
 METRIC = "env steps/sec (whole node) at 65 536 worlds; 1→8 GPU scaling"
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 EVENT_MIN_LAUNCHES = 200  # kernel-time averages over at least this many launches
+STAGE_MAX_BYTES = 8 << 30  # staged action rows resident at a time (2 730 steps at 65 536 x 2)
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: all files together (the bound is 64 MB)
 
 
 def log(*a):
@@ -105,6 +115,28 @@ def cpu_executor_baseline(num_agents: int, seconds: float, threads: int):
             "sample": f"{w} worlds x {st} steps on {threads} threads, {num_agents} agents, threefry random actions"}
 
 
+def dump_outputs(path: str, tensors: dict, num_worlds: int) -> None:
+    """Write `tensors` (name -> (tensor, its worlds axis)) as path/<name>.npy:
+    float32 as it is, integer columns as float64 (exact).  When everything
+    together would pass DUMP_MAX_BYTES, every array keeps the same sorted
+    sample of worlds, drawn with a fixed seed; worlds.npy lists the worlds kept."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays, axis = {}, {}
+    for name, (t, ax) in tensors.items():
+        a = t.detach().cpu().numpy()
+        arrays[name] = a if a.dtype == np.float32 else a.astype(np.float64)
+        axis[name] = int(ax)
+        assert a.shape[axis[name]] == num_worlds, (name, a.shape)
+    per_world = sum(a.nbytes // num_worlds for a in arrays.values()) + 8
+    keep = np.arange(num_worlds)
+    if per_world * num_worlds > DUMP_MAX_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(num_worlds, DUMP_MAX_BYTES // per_world, replace=False))
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(np.take(a, keep, axis=axis[name])))
+    np.save(os.path.join(path, "worlds.npy"), keep.astype(np.float64))
+
+
 def load_traffic(workload_key: str):
     """HBM bytes per step-kernel launch from the committed PMC passes
     (tools/traffic.py; FETCH_SIZE x2 + WRITE_SIZE), or None."""
@@ -161,6 +193,13 @@ def main():
     ap.add_argument("--worlds", type=int, default=65536, help="worlds per GPU")
     ap.add_argument("--agents", type=int, default=2)
     ap.add_argument("--seed", type=int, default=321)
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the CPU baselines, the per-call and end-to-end legs, the "
+                         "events-timed kernel passes (roofline) and the other BASELINE configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the tensors a caller of the timed path holds after its "
+                         "last step as DIR/<name>.npy (rank 0's worlds; a seeded sample of them where all "
+                         "would pass 48 MiB); the inputs are seeded, so two builds can be compared output for output")
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-procs", type=int, default=min(16, os.cpu_count() or 1),
@@ -199,7 +238,7 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     cpu = cpu_exec = None
     # the CPU baselines: rank 0 at N = 1 only, before any GPU call
-    if rank == 0 and world_size == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world_size == 1 and not args.no_cpu_baseline:
         cpu = cpu_baseline(args.agents, args.cpu_seconds, args.cpu_procs)
         cpu_exec = cpu_executor_baseline(args.agents, min(args.cpu_seconds, 8.0), args.cpu_procs)
 
@@ -267,13 +306,18 @@ def main():
         del warm
     else:
         sim.step_n(args.warmup, random_actions=True, action_seed=args.seed, step0=0)
-    staged = sim.stage_random_actions(args.steps, action_seed=args.seed, step0=args.warmup)
+    K = args.rollout
+    if K and args.steps % K:
+        raise SystemExit("--steps must be a multiple of --rollout")
+    # (a run longer than STAGE_MAX_BYTES of rows is staged and timed in chunks
+    # of that size, each staged outside its timed region)
+    chunk = max(1, min(args.steps, STAGE_MAX_BYTES // (W * args.agents * 24)))
+    if K:
+        chunk = max(K, chunk - chunk % K)
+    staged = sim.stage_random_actions(chunk, action_seed=args.seed, step0=args.warmup)
     barrier()
 
-    K = args.rollout
     if K:
-        if args.steps % K:
-            raise SystemExit("--steps must be a multiple of --rollout")
         bufs = None if args.policy else sim.rollout_buffers(K)  # reused by every chunk, like PPO's storage
 
     if args.policy:
@@ -284,19 +328,20 @@ def main():
         if K:  # PPO's rollout storage (scripts/buffers.py), reused by every chunk
             pbufs = pol.rollout_buffers(sim, K)
 
-    def run(actions, time_kernels=False, steps=None):
-        """All staged steps: one step per launch, or chunks of K via bb_rollout."""
+    def run(actions, time_kernels=False, steps=None, base=0):
+        """All staged steps: one step per launch, or chunks of K via bb_rollout
+        (`base`: the steps already run, for the policy's sampling counter)."""
         steps = args.steps if steps is None else steps
         if args.policy and K:  # PPO's rollout on the device (bb_rollout_policy), K steps per call
             ms = 0.0
             for i in range(0, steps, K):
-                ms += pol.rollout(sim, K, pbufs, trainee=0, stochastic=True, seed=args.seed, step0=i,
+                ms += pol.rollout(sim, K, pbufs, trainee=0, stochastic=True, seed=args.seed, step0=base + i,
                                   time_kernels=time_kernels) or 0.0
             return ms
         if args.policy:  # actions come from the policy, not the staged rows
             for t in range(steps):
                 for a in range(args.agents):
-                    pol.act(sim, a, lp, val, stochastic=True, seed=args.seed, step=t)
+                    pol.act(sim, a, lp, val, stochastic=True, seed=args.seed, step=base + t)
                 sim.step()
             return None
         if not K:
@@ -311,20 +356,37 @@ def main():
             ms += r or 0.0
         return ms
 
-    # timed region: exactly K steps, step k reading staged[k] (scripts/run.py:10-15)
-    t0 = time.perf_counter()
-    run(staged)
-    sync()
-    elapsed = time.perf_counter() - t0
+    # timed region: exactly --steps steps, step k reading staged[k] (scripts/run.py:10-15)
+    elapsed, ran = 0.0, 0
+    while ran < args.steps:
+        n = min(chunk, args.steps - ran)
+        if ran:
+            del staged
+            staged = sim.stage_random_actions(n, action_seed=args.seed, step0=args.warmup + ran)
+            barrier()
+        t0 = time.perf_counter()
+        run(staged, steps=n, base=ran)
+        sync()
+        elapsed += time.perf_counter() - t0
+        ran += n
     barrier()
     elapsed = max_over_ranks(elapsed)
+    if args.dump_outputs and rank == 0:
+        # the simulator's tensors ([W, ...]) and what the rollouts recorded ([K, W, ...])
+        outputs = {k: (v, 0) for k, v in sim.snapshot().items()}
+        if K and not args.policy and not args.no_record:
+            outputs.update({"rollout_" + k: (v, 1) for k, v in bufs.items()})
+        if K and args.policy:
+            outputs.update({"rollout_" + k: (v, v.dim() > 1) for k, v in pbufs.items()})
+        dump_outputs(args.dump_outputs, outputs, W)
+        del outputs
 
     # the drop-in path's own timed region: the same number of steps, each one
     # launch of the kernel SimpleGridworldSimulator.step() issues (k_step,
     # scripts/env.py:155 inside scripts/run.py:10-15's loop), reading its
     # staged action rows; bit-identical results to the headline's launch
     per_call_s = None
-    if on_gpu and not K and not args.policy:
+    if args.full and on_gpu and not K and not args.policy:
         del staged
         staged = sim.stage_random_actions(args.steps, action_seed=args.seed, step0=args.warmup + args.steps)
         with _lib.diag(step_loop=0):
@@ -345,7 +407,7 @@ def main():
     L = _lib.load()
     staged_path = int(L.bb_step_staged_path(sim._h, max(args.steps, EVENT_MIN_LAUNCHES)))
     loop_main = on_gpu and not K and not args.policy and staged_path != 0
-    if on_gpu and (not args.policy or K):
+    if args.full and on_gpu and (not args.policy or K):
         per_launch = K if (K and (fused or args.policy)) else 1
         ev_steps = max(args.steps, EVENT_MIN_LAUNCHES * per_launch)
         if K:
@@ -385,7 +447,7 @@ def main():
     # tensor by a torch slice assignment, SimpleGridworldSimulator.step() is
     # called from Python, and obs / reward / done of the trainee are cloned
     e2e = None
-    if not args.no_e2e and not args.policy and not K:
+    if args.full and not args.no_e2e and not args.policy and not K:
         import torch
         views = {k: getattr(sim, k)().to_torch() for k in
                  ("action_tensor", "observations_tensor", "reward_tensor", "done_tensor")}
@@ -429,7 +491,7 @@ def main():
     # "5v5" extensions (65 536 x 4 / x 10); each events-timed over
     # >= EVENT_MIN_LAUNCHES launches like the headline kernel
     extra = {}
-    if (on_gpu and not args.no_configs and not args.policy and not K
+    if (args.full and on_gpu and not args.no_configs and not args.policy and not K
             and W == 65536 and args.agents == 2):
         L0 = _lib.load()
 
@@ -649,7 +711,7 @@ def main():
             "algorithmic_bytes_per_launch": bytes_per_launch,
         },
     }
-    if loop_main and on_gpu:
+    if loop_main and args.full:
         # kernel_avg_us (and achieved / frac) are per step: one k_step_loop
         # launch's events over its steps (rocprof shows the launch: x steps)
         out["roofline"]["algorithmic_bytes_per_step"] = bytes_per_launch
@@ -669,12 +731,14 @@ def main():
                 "achieved": b1 / reload_s / 1e9, "frac": b1 / reload_s / 1e9 / HBM_PEAK_GBS,
                 "what": "the same steps with every state column reloaded each step (k_step_loop, step_loop path "
                         "override = 1)"}
+    if not args.full:
+        out["roofline"] = None  # its kernel time is an events-timed pass of its own
     if not on_gpu:
         out["roofline"] = None
         out["config"]["parallelism"] += " (host executor, gloo)"
     if args.policy:
         out["roofline"] = None  # several kernels per step: see the rocprof summary
-        if K and on_gpu:
+        if K and on_gpu and args.full:
             out["policy_rollout"] = {"rollout_avg_us": avg_kernel_s * 1e6, "us_per_step": avg_kernel_s * 1e6 / K,
                                      "rollouts_timed": launches,
                                      "timing": "events around each bb_rollout_policy call (its K policy passes, "

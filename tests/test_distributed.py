@@ -33,7 +33,8 @@ def test_bench_two_ranks_gloo():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="1", BB_CPU_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--exec", "cpu", "--worlds", "512", "--steps", "20", "--warmup", "2", "--cpu-seconds", "0.5", "--cpu-procs", "1"]
+           "--gpus", "2", "--full", "--exec", "cpu", "--worlds", "512", "--steps", "20", "--warmup", "2",
+           "--cpu-seconds", "0.5", "--cpu-procs", "1"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -16,7 +16,7 @@ for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_
            "FETCH_SIZE" "WRITE_SIZE"; do
     i=$((i+1))
     timeout -s KILL 120 rocprofv3 --pmc $grp -d "$OUT/g$i" -o run --output-format csv -- \
-        python3 "$ROOT/bench.py" --no-cpu-baseline "$@" > "$OUT/g$i.log" 2>&1
+        python3 "$ROOT/bench.py" --full --no-cpu-baseline "$@" > "$OUT/g$i.log" 2>&1
     rc=$?
     echo "group $i ($grp) rc=$rc"
     [ $rc -ne 0 ] && exit $rc
