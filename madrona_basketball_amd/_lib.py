@@ -154,6 +154,7 @@ DIAG_KEYS = {
     "ppo_step_fused_min_worlds": 6,  # the fused PPO step from this many worlds (0: never)
     "ppo_step_loop": 7,              # 0: one k_step_ppo launch per step
     "policy_wg": 8,                  # k_policy_wg: 0 never, 1 always
+    "ppo_opp_waves": 9,              # k_rollout_selfplay's opponent waves: 1 or 2
 }
 
 

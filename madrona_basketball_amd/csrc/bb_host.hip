@@ -1026,7 +1026,11 @@ static int32_t ppo_path(const bb_sim *s, bool opponent, uint32_t flags)
     if (s->cfg.exec_mode != BB_EXEC_CUDA) return BB_PPO_PATH_HOST;
     if (s->n != 2) return -1;  // bb_rollout_policy: the reference's 2-agent game only
     const int64_t W = s->cfg.num_worlds;
-    if (!(flags & BB_ROLLOUT_PER_STEP) && !opponent && bb::fused_rollout_n(s->n) && W <= ppo_fused_max_worlds())
+    // with an opponent too (k_rollout_selfplay), to the same bound: measured
+    // per step, K = 32, 8 192 worlds 10.5 us against 31.4 for the per-step
+    // launches, 16 384 worlds 15.4 against 37.5 (profiles/r07/selfplay_ab.txt);
+    // above the bound an opponent keeps the per-step launches
+    if (!(flags & BB_ROLLOUT_PER_STEP) && bb::fused_rollout_n(s->n) && W <= ppo_fused_max_worlds())
         return BB_PPO_PATH_FUSED_ROLLOUT;
     if (!(flags & BB_ROLLOUT_PER_STEP) && !opponent && s->n == 2 && ppo_step_fused_min_worlds() > 0 &&
         W >= ppo_step_fused_min_worlds())
@@ -1119,6 +1123,10 @@ int bb_rollout_policy(bb_sim *s, const bb_policy_weights *w, const bb_policy_wei
         r.obs_out = out->obs; r.act_out = out->actions; r.log_prob = out->log_prob; r.value = out->value;
         r.reward = out->reward; r.done = out->done; r.next_value = out->next_value;
         r.steps = n; r.trainee = trainee; r.stochastic = stochastic ? 1 : 0; r.seed = seed; r.step0 = step0;
+        if (opponent) {
+            r.opp = policy_weights(opponent);
+            r.has_opp = 1;
+        }
         hipError_t e = bb::launch_rollout_policy(s->n, s->p, r, st);
         if (e != hipSuccess) return hip_fail(e, "launch fused PPO rollout kernel");
     }
@@ -1631,7 +1639,9 @@ int64_t bb_rollout_policy_bytes(const bb_sim *s, int32_t with_opponent, uint32_t
     case BB_PPO_PATH_FUSED_ROLLOUT:
         // state in once and out once (every row of the last step included); per
         // step the policy's records and the step's reward / done
-        return B + (int64_t)n * (rec + outs + rd) + 4;
+        // (self-play: plus the other agent's step-0 rows, read once by the
+        // opponent's waves; nothing of the opponent moves per step)
+        return B + (with_opponent ? rec : 0) + (int64_t)n * (rec + outs + rd) + 4;
     case BB_PPO_PATH_FUSED_STEP:
         // what the call must move, not what the launch does: the state in once
         // and out once (B, the last step's rows included), the trainee's rows

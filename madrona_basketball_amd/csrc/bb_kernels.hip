@@ -1114,10 +1114,46 @@ __device__ __forceinline__ void ppo_x_pass(const World<2> &v, const Ctx &c, cons
     }
 }
 
-template <int N, int PW>
-__device__ __forceinline__ void ppo_sim_wave(const Params &p, const PolicyRolloutArgs &r, PpoLds<PW> &L, float *tile)
+// Self-play (k_rollout_selfplay): what the frozen opponent's OW waves and the
+// sim wave share -- the other agent's rows, its actions, the opponent's
+// normalisation constants, its hidden / logit tiles and bucket scratch.  A
+// struct of its own, so that PpoLds (the kernels without an opponent) keeps
+// its size.
+template <int OW>
+struct PpoOppLds {
+    float x[32][PPO_XS];
+    int32_t act[32][6];
+    float norm[2][POL_IN];
+    float ptile[32][33];  // both M-tiles' hidden activations, then logits
+    BucketLds<32 / OW> bucket[OW];
+};
+
+// Self-play: pass P of the lane's own agent's row into xr (the trainee's lane
+// into X, the other lane into the opponent's tile): every lane emits one row,
+// no lane pair shares one.  A non-canonical world's whole row in pass 0.
+template <int P>
+__device__ __forceinline__ void ppo_own_x_pass(const World<2> &v, const Ctx &c, const SharedObs<2> &sh, bool active,
+                                               bool share, bool fast, float *xr, int32_t ib)
+{
+    if (!active) return;
+    if (fast) {
+        XPassSink<P, -1> o;
+        o.row = xr; o.idx = 0; o.b0 = o.b1 = o.b2 = o.b3 = 0.f;
+        if (share) emit_row_shared(v, c, sh, 0, o, ib);
+        else emit_row_fast(v, c, 0, o, ib);
+    } else if (P == 0) {
+        fill_obs_slow(v, c, 0, xr, ib);
+    }
+}
+
+// OL: PpoOppLds<OW> of the self-play kernel (the opponent's actions injected
+// beside the trainee's, both agents' rows emitted), or void: no opponent.
+template <int N, int PW, class OL = void>
+__device__ __forceinline__ void ppo_sim_wave(const Params &p, const PolicyRolloutArgs &r, PpoLds<PW> &L, float *tile,
+                                             OL *O = nullptr)
 {
     static_assert(N == 2, "the reference's 2-agent game");
+    constexpr bool OPP = !std::is_void<OL>::value;
     const int lane = threadIdx.x;
     const int64_t w0 = (int64_t)blockIdx.x * (WAVE / N);
     const int64_t w = w0 + lane / N;
@@ -1165,6 +1201,14 @@ __device__ __forceinline__ void ppo_sim_wave(const Params &p, const PolicyRollou
             for (int i = 0; i < N; i++)
 #pragma unroll
                 for (int q = 0; q < 6; q++) s.act[i][q] = i == trainee ? a[q] : s.act[i][q];
+            if constexpr (OPP) {  // the frozen opponent's actions for the other agent (env.py:127-143)
+#pragma unroll
+                for (int q = 0; q < 6; q++) a[q] = O->act[wl][q];
+#pragma unroll
+                for (int i = 0; i < N; i++)
+#pragma unroll
+                    for (int q = 0; q < 6; q++) s.act[i][q] = i == trainee ? s.act[i][q] : a[q];
+            }
             step_world_pre_obs(s, c, ag);
             ib = inbounder_id(s);
             share = obs_sharable(s);
@@ -1176,7 +1220,7 @@ __device__ __forceinline__ void ppo_sim_wave(const Params &p, const PolicyRollou
         const bool is_trainee = k == trainee;
         const bool fast = active && canonical_slots(v, 0);
         const bool split = share && fast;  // uniform over the world's two lanes
-        if (active && split && !is_trainee) {
+        if (!OPP && active && split && !is_trainee) {
             // the trainee's direction / distance to this lane's agent, as the
             // trainee's lane computes them (lane_shared_obs: to = other - self)
             const F3 to = v.pos(0) - v.pos(1);
@@ -1186,11 +1230,14 @@ __device__ __forceinline__ void ppo_sim_wave(const Params &p, const PolicyRollou
             sh.rlen[1][0] = bbm::sqrtf_(l2);
         }
         float *xr = L.x[wl];
+        if constexpr (OPP) xr = is_trainee ? xr : O->x[wl];  // each lane its own agent's row
         lds_barrier();  // X is free: the policy waves have recorded buffer.obs[t] from it
-        ppo_x_pass<0>(v, c, sh, active, is_trainee, split, fast, xr, ib);
+        if constexpr (OPP) ppo_own_x_pass<0>(v, c, sh, active, share, fast, xr, ib);
+        else ppo_x_pass<0>(v, c, sh, active, is_trainee, split, fast, xr, ib);
         wave_sync();
         lds_barrier();  // pass 0 of X: the policy waves start layer 1
-        ppo_x_pass<1>(v, c, sh, active, is_trainee, split, fast, xr, ib);
+        if constexpr (OPP) ppo_own_x_pass<1>(v, c, sh, active, share, fast, xr, ib);
+        else ppo_x_pass<1>(v, c, sh, active, is_trainee, split, fast, xr, ib);
         wave_sync();
         lds_barrier();  // X holds the observations after step t
         if (t + 1 == r.steps) {  // the sim's observation tensor: every row of the last step
@@ -1318,6 +1365,91 @@ __global__ __launch_bounds__(WAVE * (1 + PW), MINW) void k_rollout_policy(const 
         const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / WAVE);
         if (wave == 0) ppo_sim_wave<N, PW>(p, r, L, (float *)tile4);
         else ppo_policy_wave<PW>(p, r, L, wave - 1);
+    }
+}
+
+// ------------------------------------------------------------------ PPO self-play rollout
+// k_rollout_selfplay<2, MINW, OW>: k_rollout_policy<2, MINW, 2> with the frozen
+// opponent of scripts/env.py:104-143 in the launch (bb_rollout_policy with an
+// opponent): 3 + OW waves per 32 worlds -- the sim wave S, the trainee's two
+// policy waves T (ppo_policy_wave<2>, unchanged) and OW opponent waves O with
+// the opponent's B operands in registers.  S emits both agents' rows after a
+// step, each lane its own agent's (the trainee's into X, the other's into
+// PpoOppLds::x), in the same two hand-offs; O runs the opponent's network on
+// its rows -- OW = 1: both 16-row M-tiles one after the other and one 32-row
+// bucket pass, OW = 2: an M-tile and a 16-row bucket pass per wave -- and only
+// the action half of the bucket pass (bucket_pass_act, always sampling, key
+// seed ^ 0x9E3779B9, the uniforms drawn a step ahead): nothing of the opponent
+// is recorded.  S injects both action rows before the step.  The network is
+// policy_layers1_split / bucket_pass_act on the rows k_policy would read, so
+// every bit equals the per-step launches'.
+//
+// Workgroup barriers per role (every role passes 3 + 4 K of them):
+//            | setup | step 0 rows | per step t = 0..K-1                        | value pass
+//   S        |   1   |   2 (idle)  | actions, X free, row pass 0, row pass 1    |    --
+//   T (x 2)  |   1   |     --      | row pass 0, row pass 1, actions, X free    | pass 0, pass 1
+//   O (x OW) |   1   |     --      | row pass 0, row pass 1, actions, X free    | pass 0, pass 1 (idle)
+// S's two idle barriers after setup stand for step 0's row passes (T and O
+// loaded those rows from the sim's tensor before the setup barrier); its last
+// two row passes pair with the value pass's.  With OW = 1 the second M-tile's
+// rows are complete when O reaches it: no barrier of its own.
+template <int OW>
+__device__ __forceinline__ void ppo_opponent_wave(const Params &p, const PolicyRolloutArgs &r, PpoOppLds<OW> &O, int ow)
+{
+    constexpr int RW = 32 / OW;  // this wave's rows
+    const int lane = threadIdx.x % WAVE, c = lane & 15, q = lane >> 4;
+    const int64_t W = p.num_worlds;
+    const int rb = RW * ow;                                  // its first row of the 32
+    const int64_t row0 = (int64_t)blockIdx.x * 32 + rb;      // that row's world
+    for (int k = ow * WAVE + lane; k < POL_IN; k += OW * WAVE) {
+        O.norm[0][k] = r.opp.obs_mean[k];
+        O.norm[1][k] = r.opp.obs_inv[k];
+    }
+    PolicyRegs R;
+    load_policy_regs(R, r.opp, c, q);
+    // step 0: the other agent's rows of the sim's observation tensor (zero tail included)
+    for (int i = lane; i < RW * 32; i += WAVE) {
+        const int rr = rb + i / 32, qq = i % 32;
+        const int64_t wg = (int64_t)blockIdx.x * 32 + rr;
+        float4 v4 = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (wg < W) v4 = *(const float4 *)(p.c.obs + (wg * 2 + (1 - r.trainee)) * (int64_t)obs_width(2) + 4 * qq);
+        *(float4 *)&O.x[rr][4 * qq] = v4;
+    }
+    __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0)
+    lds_barrier();  // setup
+    PolicyArgs a{};
+    a.rows = W;
+    a.stochastic = 1;  // the frozen policy samples (Agent.forward's default) with its own key
+    a.seed = r.seed ^ 0x9E3779B9u;
+    BucketNoise<RW> noise;
+    bucket_noise<RW>(noise, a.seed, r.step0, row0, W, lane);
+    for (int t = 0; t < r.steps; t++) {
+        lds_barrier();  // pass 0 of the rows
+        policy_layers1_split(&O.x[rb + c][0], R, O.norm, O.ptile + rb, c, q, [] { lds_barrier(); /* pass 1 */ });
+        if constexpr (OW == 1) policy_layers1_split(&O.x[16 + c][0], R, O.norm, O.ptile + 16, c, q, [] {});
+        a.step = r.step0 + (uint32_t)t;
+        BucketHold<RW> hold;
+        bucket_pass_act<RW, true>(a, O.ptile + rb, row0, lane, O.bucket[ow], O.act + rb, &noise, hold);
+        pol_wave_sync();
+        lds_barrier();  // actions in LDS
+        if (t + 1 < r.steps) bucket_noise<RW>(noise, a.seed, r.step0 + (uint32_t)(t + 1), row0, W, lane);
+        lds_barrier();  // X free
+    }
+    lds_barrier();  // (the trainee's value pass: its two row hand-offs)
+    lds_barrier();
+}
+
+template <int N, int MINW, int OW>
+__global__ __launch_bounds__(WAVE * (3 + OW), MINW) void k_rollout_selfplay(const Params p, const PolicyRolloutArgs r)
+{
+    if constexpr (N == 2 && FusedRollout<N>::value) {
+        __shared__ PpoLds<2> L;
+        __shared__ PpoOppLds<OW> O;
+        __shared__ float4 tile4[StepTile<N, false>::FLOATS / 4];
+        const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / WAVE);
+        if (wave == 0) ppo_sim_wave<N, 2>(p, r, L, (float *)tile4, &O);
+        else if (wave < 3) ppo_policy_wave<2>(p, r, L, wave - 1);
+        else ppo_opponent_wave<OW>(p, r, O, wave - 3);
     }
 }
 
@@ -2813,6 +2945,24 @@ hipError_t launch_rollout_policy_t(const Params &p, const PolicyRolloutArgs &r, 
         // per call 22.3 + 8.99 us per step vs 18.9 + 8.84); 16 384: 18.2 vs 12.1.
         // DIAG_PPO_PWAVES = 2 / 4 forces it (tests).
         const dim3 grid((unsigned)((p.num_worlds + 31) / 32));
+        if (r.has_opp) {
+            // self-play: two opponent waves (5 waves per workgroup, the
+            // 256-register budget) while the grid is one workgroup per CU,
+            // one (4 waves: 8 per CU at two workgroups) above -- at one
+            // workgroup per CU the 4-wave form gives every wave a SIMD and
+            // its whole register file, no spill, and is still slower: the
+            // opponent wave's two M-tiles in turn are the step's longest
+            // chain (8 192 worlds 12.2 vs 10.5 us per step,
+            // profiles/r07/selfplay_ab.txt).  DIAG_PPO_OPP_WAVES = 1 / 2
+            // forces it (tests, A/B timing).
+            const int ow = diag_or(DIAG_PPO_OPP_WAVES, PPO_OPP_WAVES);
+            if (ow == 2 && grid.x <= device_cus())
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_selfplay<N, 2, 2>), grid, dim3(WAVE * 5), 0, s, p, r);
+            else if (grid.x <= device_cus())
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_selfplay<N, 1, 1>), grid, dim3(WAVE * 4), 0, s, p, r);
+            else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_selfplay<N, 2, 1>), grid, dim3(WAVE * 4), 0, s, p, r);
+            return hipGetLastError();
+        }
         const int forced = diag_or(DIAG_PPO_PWAVES, 0);
         const int pw = forced == 2 || forced == 4 ? forced : 2;
         if (pw == 4)

@@ -51,7 +51,18 @@ struct PolicyRolloutArgs {
     float *next_value;    // [W]
     int32_t steps, trainee, stochastic;
     uint32_t seed, step0;
+    // self-play (k_rollout_selfplay<2>): the frozen opponent's policy acts for
+    // the other agent on every step (sampling, key seed ^ 0x9E3779B9); nothing
+    // of it is recorded
+    PolicyWeights opp;
+    int32_t has_opp;
 };
+// Opponent waves per 32 worlds of the self-play rollout while its grid is one
+// workgroup per CU (above: 1): measured at 8 192 worlds, K = 32, all records,
+// 10.51-10.55 us per step with 2 (one 16-row M-tile each, 5 waves, 256
+// registers) against 12.20-12.25 with 1 (both M-tiles in turn, 4 waves, no
+// spill) -- profiles/r07/selfplay_ab.txt.  DIAG_PPO_OPP_WAVES overrides it.
+constexpr int PPO_OPP_WAVES = 2;
 
 // One step of PPO's rollout loop with the policy fused behind it
 // (k_step_ppo<2> / k_rollout_ppo<2>, bb_rollout_policy above 16 384 worlds): step k on the
@@ -109,7 +120,8 @@ enum DiagKey : int {
     DIAG_PPO_STEP_FUSED_MIN_WORLDS = 6,  // the fused PPO step from this many worlds (default 1; 0 never)
     DIAG_PPO_STEP_LOOP = 7,              // 0: one k_step_ppo launch per step instead of one k_rollout_ppo
     DIAG_POLICY_WG = 8,                  // k_policy_wg: 0 never, 1 always (else from 98 304 rows)
-    DIAG_KEYS = 9
+    DIAG_PPO_OPP_WAVES = 9,              // k_rollout_selfplay's opponent waves: 1 or 2 (2 only at one workgroup per CU)
+    DIAG_KEYS = 10
 };
 extern int diag_override[DIAG_KEYS];
 inline int diag_or(int key, int dflt)

@@ -199,8 +199,10 @@ class FusedPolicy:
         buffer stores of ppo.py:129-134 and next_value = evaluate(last obs).
         Bit for bit n x (act(); [opponent.act()]; sim.step()) with the same reads.
         Any entry of `buffers` may be None (not recorded).  On gfx950 (2 agents,
-        no opponent, up to 16 384 worlds) one fused launch runs every step;
-        per_step=True forces a policy launch + a step launch per step.  Returns
+        up to 16 384 worlds) one fused launch runs every step, with the
+        opponent's network in it when there is one (nothing of the opponent is
+        recorded); per_step=True forces a policy launch per acting agent + a
+        step launch per step.  Returns
         the elapsed device ms when time_kernels."""
         W = sim.num_worlds
         shapes = {"obs": ((n, W, IN), torch.float32), "actions": ((n, W, 6), torch.int32),
