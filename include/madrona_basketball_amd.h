@@ -293,6 +293,43 @@ int bb_rollout_policy(bb_sim *sim, const bb_policy_weights *w, const bb_policy_w
 int32_t bb_rollout_policy_path(const bb_sim *sim, int32_t with_opponent, uint32_t flags);
 int64_t bb_rollout_policy_bytes(const bb_sim *sim, int32_t with_opponent, uint32_t flags, int32_t n);
 
+/* PPO's minibatch update up to param.grad (scripts/ppo.py:190-213 update_policy:
+ * buffer.get_minibatch scripts/buffers.py:25-33, agent.get_stats
+ * scripts/agent.py:172-178 over scripts/action.py:35-44, the clipped surrogate,
+ * clipped value and entropy losses ppo.py:195-210 with clip_vloss, backward()):
+ * forward, loss and backward of the policy network over the m minibatch rows
+ * in one pass.  The batch is the rollout buffer's flat view: obs float
+ * [rows][128] (16-byte aligned), actions int32 [rows][6], log_prob / value /
+ * advantages / returns float [rows]; idx int64 [m] the minibatch's buffer rows
+ * (mb_inds; NULL: rows 0..m-1), gathered by the kernel.  An index outside
+ * [0, rows) contributes nothing.  Writes d loss / d parameter for the weights
+ * `w` into `grads` (bb_policy_weights without the normaliser, whose statistics
+ * are not parameters; head rows 0-18 the actor, 19 the critic, 20-31 zero) and
+ * loss4 = {loss, pg_loss, c_loss before vf_coef, mean entropy}, with
+ * loss = pg_loss + vf_coef c_loss - ent_coef entropy (ppo.py:206-210).
+ * workspace: bb_policy_ppo_grad_workspace_bytes(m) bytes on the device,
+ * 16-byte aligned (CUDA mode; unused in CPU mode, may be NULL there).  No
+ * atomics: the same inputs give the same bits.  No synchronisation. */
+typedef struct bb_ppo_batch {
+    const float *obs;
+    const int32_t *actions;
+    const float *log_prob, *value, *advantages, *returns;
+    const int64_t *idx;
+    int64_t rows, m;
+} bb_ppo_batch;
+typedef struct bb_ppo_coef {
+    float clip_coef, vf_coef, ent_coef;
+} bb_ppo_coef;
+typedef struct bb_policy_grads {
+    float *w1, *b1, *ln1_w, *ln1_b;
+    float *w2, *b2, *ln2_w, *ln2_b;
+    float *head_w, *head_b;
+} bb_policy_grads;
+int bb_policy_ppo_grad(const bb_policy_weights *w, int32_t exec_mode, int32_t gpu_id, const bb_ppo_batch *batch,
+                       const bb_ppo_coef *coef, bb_policy_grads *grads, float *loss4, void *workspace,
+                       int64_t workspace_bytes, void *stream);
+int64_t bb_policy_ppo_grad_workspace_bytes(int64_t m);
+
 int bb_set_action(bb_sim *sim, int32_t world_idx, int32_t agent_idx, int32_t move_speed,
                   int32_t move_angle, int32_t rotate, int32_t grab, int32_t pass,
                   int32_t shoot, void *stream);

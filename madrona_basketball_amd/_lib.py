@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "bb_create_with_buffers", "bb_destroy", "bb_step", "bb_step_n",
     "bb_write_random_actions", "bb_step_n_staged", "bb_fill_random_actions", "bb_rollout",
     "bb_record_words", "bb_record", "bb_policy_forward", "bb_rollout_policy",
+    "bb_policy_ppo_grad", "bb_policy_ppo_grad_workspace_bytes",
     "bb_set_action", "bb_trigger_reset", "bb_export",
     "bb_num_worlds", "bb_num_agents", "bb_exec_mode", "bb_algorithmic_bytes_per_world",
     "bb_rollout_policy_path", "bb_rollout_policy_bytes", "bb_step_staged_path", "bb_step_staged_bytes",
@@ -71,6 +72,21 @@ class PolicyWeights(ctypes.Structure):
 class PolicyRolloutBuffers(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("obs", "actions", "log_prob", "value", "reward", "done",
                                                "next_value")]
+
+
+class PpoBatch(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("obs", "actions", "log_prob", "value", "advantages", "returns",
+                                                "idx")]
+                + [("rows", ctypes.c_int64), ("m", ctypes.c_int64)])
+
+
+class PpoCoef(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_float) for n in ("clip_coef", "vf_coef", "ent_coef")]
+
+
+class PolicyGrads(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("w1", "b1", "ln1_w", "ln1_b", "w2", "b2", "ln2_w", "ln2_b",
+                                               "head_w", "head_b")]
 
 
 _lib = None
@@ -114,6 +130,9 @@ def load():
         "bb_rollout_policy": (ctypes.c_int, [vp, ctypes.POINTER(PolicyWeights), ctypes.POINTER(PolicyWeights), i32,
                                              i32, i32, u32, u32, ctypes.POINTER(PolicyRolloutBuffers), u32, vp,
                                              ctypes.POINTER(ctypes.c_float)]),
+        "bb_policy_ppo_grad": (ctypes.c_int, [ctypes.POINTER(PolicyWeights), i32, i32, ctypes.POINTER(PpoBatch),
+                                              ctypes.POINTER(PpoCoef), ctypes.POINTER(PolicyGrads), vp, vp, i64, vp]),
+        "bb_policy_ppo_grad_workspace_bytes": (i64, [i64]),
         "bb_set_action": (ctypes.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "bb_trigger_reset": (ctypes.c_int, [vp, i32, vp]),
         "bb_export": (ctypes.c_int, [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(i32),

@@ -193,6 +193,11 @@ hipError_t launch_random_actions(int n, const Params &p, uint32_t seed, uint32_t
 hipError_t launch_poke(int32_t *dst, int count, const int32_t *vals, hipStream_t s);
 hipError_t launch_policy(const PolicyArgs &a, hipStream_t s);
 void host_policy(const PolicyArgs &a);
+// PPO's minibatch loss and gradient (bb_policy_grad.h / bb_policy_grad.hip)
+struct PpoGradArgs;
+hipError_t launch_ppo_grad(const PpoGradArgs &a, hipStream_t s);
+void host_ppo_grad(const PpoGradArgs &a);
+int64_t ppo_grad_workspace_bytes(int64_t m);
 hipError_t launch_record(const RecordArgs &a, int64_t world0, int32_t count, uint32_t *dst, hipStream_t s);
 void host_record(const RecordArgs &a, int64_t world0, int32_t count, uint32_t *dst);
 // diagnostics: the step's scalar math on the device (bb_diag_math)

@@ -174,6 +174,78 @@ class FusedPolicy:
         act = sim.action_tensor().to_torch()[:, agent_idx]
         self.forward_into(obs, act, log_prob, value, stochastic, seed, step)
 
+    # ------------------------------------------------------------- PPO update
+    def ppo_grad(self, obs: torch.Tensor, actions: torch.Tensor, log_prob: torch.Tensor, value: torch.Tensor,
+                 advantages: torch.Tensor, returns: torch.Tensor, idx: torch.Tensor = None, clip_coef: float = 0.2,
+                 vf_coef: float = 1.0, ent_coef: float = 0.01) -> torch.Tensor:
+        """One minibatch of update_policy up to loss.backward() (scripts/ppo.py:190-213,
+        clip_vloss) in one pass on the device, bb_policy_ppo_grad: the rows `idx`
+        (int64 [M], mb_inds; None: all R) of the rollout buffer's flat views -- obs
+        float32 [R, 128], actions int32 [R, 6], log_prob / value / advantages /
+        returns float32 [R] (scripts/buffers.py:25-33; the rollout_buffers tensors
+        reshape to them without a copy) -- are gathered by the kernel, and the
+        gradient of ppo.py:210's loss at the weights last packed by refresh() is
+        left in .grad of the agent's 12 parameter tensors (overwritten), for
+        clip_grad_norm_ and optimizer.step() to go on from.  Returns a float32 [4]
+        tensor on the device: loss, pg_loss, c_loss before vf_coef, mean entropy
+        (no host synchronisation).  head_grad keeps the packed head's gradient
+        ([32, 32] and [32]: rows 0-18 the actor, 19 the critic, 20-31 zero)."""
+        dev, f32 = self.device, torch.float32
+        if obs.dim() != 2 or obs.shape[1] != IN or obs.dtype != f32 or not obs.is_contiguous():
+            raise ValueError("obs must be a contiguous float32 [rows, 128] tensor")
+        rows = obs.shape[0]
+        if tuple(actions.shape) != (rows, 6) or actions.dtype != torch.int32 or not actions.is_contiguous():
+            raise ValueError("actions must be a contiguous int32 [rows, 6] tensor")
+        for t in (log_prob, value, advantages, returns):
+            if tuple(t.shape) != (rows,) or t.dtype != f32 or not t.is_contiguous():
+                raise ValueError("log_prob, value, advantages and returns must be contiguous float32 [rows]")
+        if idx is not None and (idx.dim() != 1 or idx.dtype != torch.int64 or not idx.is_contiguous()):
+            raise ValueError("idx must be a contiguous int64 [M] tensor")
+        m = rows if idx is None else idx.shape[0]
+        if rows < 1 or m < 1:
+            raise ValueError("an empty minibatch")
+        for t in (obs, actions, log_prob, value, advantages, returns, idx):
+            if t is not None and t.device != dev:
+                raise ValueError("all tensors must live on the policy's device")
+        a = self.agent
+        lin = [mod for mod in a.backbone if isinstance(mod, torch.nn.Linear)]
+        lns = [mod for mod in a.backbone if isinstance(mod, torch.nn.LayerNorm)]
+        direct = [lin[0].weight, lin[0].bias, lns[0].weight, lns[0].bias,
+                  lin[1].weight, lin[1].bias, lns[1].weight, lns[1].bias]
+        heads = [a.actor.weight, a.critic.weight, a.actor.bias, a.critic.bias]
+        if tuple(direct[0].shape) != (HID, IN) or tuple(direct[4].shape) != (HID, HID) or a.actor.out_features != LOGITS:
+            raise ValueError("FusedPolicy supports the reference configuration: input 128, num_channels 32, "
+                             "num_layers 2, buckets [2, 8, 3, 2, 2, 2] (scripts/env.py:107)")
+        for p in direct + heads:
+            if p.device != dev or p.dtype != f32:
+                raise ValueError("the agent's parameters must be float32 on the policy's device")
+            if p.grad is None or not p.grad.is_contiguous():
+                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+        lib = _lib.load()
+        cuda = dev.type == "cuda"
+        need = lib.bb_policy_ppo_grad_workspace_bytes(m) if cuda else 0
+        if getattr(self, "_ppo_ws", None) is None or self._ppo_ws.numel() * 4 < need:
+            self._ppo_ws = torch.empty((max(need, 4) // 4,), dtype=f32, device=dev)
+        if getattr(self, "head_grad", None) is None:
+            self.head_grad = (torch.zeros((HEAD, HID), dtype=f32, device=dev), torch.zeros((HEAD,), dtype=f32, device=dev))
+        hw, hb = self.head_grad
+        loss4 = torch.empty((4,), dtype=f32, device=dev)
+        batch = _lib.PpoBatch(obs.data_ptr(), actions.data_ptr(), log_prob.data_ptr(), value.data_ptr(),
+                              advantages.data_ptr(), returns.data_ptr(), None if idx is None else idx.data_ptr(),
+                              rows, m)
+        coef = _lib.PpoCoef(float(clip_coef), float(vf_coef), float(ent_coef))
+        grads = _lib.PolicyGrads(*[p.grad.data_ptr() for p in direct], hw.data_ptr(), hb.data_ptr())
+        _lib.check(lib.bb_policy_ppo_grad(
+            ctypes.byref(self._w), int(ExecMode.CUDA if cuda else ExecMode.CPU),
+            dev.index if dev.index is not None else -1, ctypes.byref(batch), ctypes.byref(coef), ctypes.byref(grads),
+            ctypes.c_void_p(loss4.data_ptr()), ctypes.c_void_p(self._ppo_ws.data_ptr() if cuda else None),
+            need, self._stream()), "policy_ppo_grad")
+        a.actor.weight.grad.copy_(hw[:LOGITS])
+        a.critic.weight.grad.copy_(hw[LOGITS:LOGITS + 1])
+        a.actor.bias.grad.copy_(hb[:LOGITS])
+        a.critic.bias.grad.copy_(hb[LOGITS:LOGITS + 1])
+        return loss4
+
     # ------------------------------------------------------------ PPO rollout
     ROLLOUT_KEYS = ("obs", "actions", "log_prob", "value", "reward", "done", "next_value")
 
