@@ -330,6 +330,41 @@ int bb_policy_ppo_grad(const bb_policy_weights *w, int32_t exec_mode, int32_t gp
                        int64_t workspace_bytes, void *stream);
 int64_t bb_policy_ppo_grad_workspace_bytes(int64_t m);
 
+/* PPO's phase between the rollout and the minibatch updates (scripts/ppo.py:144-177
+ * compute_advantages over scripts/agent.py:28-50 RunningMeanStd), on the
+ * buffers bb_rollout_policy filled: obs float [steps][worlds][128] (16-byte
+ * aligned), value / reward / done float [steps][worlds], next_value float
+ * [worlds].  With m = (float)value_norm.mean, s = (float)value_norm.var + 1e-5f:
+ *   v = m + sqrt(s) clamp(value, +-5), nv likewise              (agent.py:31-34)
+ *   GAE backwards over the steps, A and Rt = A + v              (ppo.py:153-166;
+ *     the last step takes 1 - done[steps-1] as its non-terminal flag, ppo.py:157)
+ *   obs_norm.update(obs rows), value_norm.update(v), value_norm.update(Rt)
+ *     in this order, each from the batch mean and unbiased variance, merged in
+ *     double in place                           (ppo.py:168-170, agent.py:41-50)
+ *   advantages = (A - mu) / (sigma + 1e-8), mu / sigma the mean and unbiased
+ *     std of A; returns = clamp((Rt - m') rsqrt(s'), +-5) with m', s' of the
+ *     updated value_norm                                        (ppo.py:173-176)
+ * `value` is not written (ppo.py:175 writes to a temporary).  out4 = {mu, sigma,
+ * value_norm's new mean, new var}.  A bb_running_stats holds device (CUDA mode)
+ * or host pointers to RunningMeanStd's double buffers: mean[dim], var[dim],
+ * count[1], 8-byte aligned; dim 1 for value_norm, 128 for obs_norm.
+ * steps x worlds >= 2.  workspace: bb_policy_advantages_workspace_bytes(steps,
+ * worlds) bytes on the device, 16-byte aligned (CUDA mode; unused in CPU mode,
+ * may be NULL there; 0 for a shape the entry refuses).  No atomics: the same
+ * inputs give the same bits.  No synchronisation. */
+typedef struct bb_running_stats {
+    double *mean, *var, *count;
+} bb_running_stats;
+typedef struct bb_adv_batch {
+    const float *obs, *value, *reward, *done, *next_value;
+    float *advantages, *returns;
+    int64_t steps, worlds;
+} bb_adv_batch;
+int bb_policy_advantages(int32_t exec_mode, int32_t gpu_id, const bb_adv_batch *batch,
+                         const bb_running_stats *value_norm, const bb_running_stats *obs_norm, double gamma,
+                         double gae_lambda, float *out4, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t bb_policy_advantages_workspace_bytes(int64_t steps, int64_t worlds);
+
 int bb_set_action(bb_sim *sim, int32_t world_idx, int32_t agent_idx, int32_t move_speed,
                   int32_t move_angle, int32_t rotate, int32_t grab, int32_t pass,
                   int32_t shoot, void *stream);

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "bb_write_random_actions", "bb_step_n_staged", "bb_fill_random_actions", "bb_rollout",
     "bb_record_words", "bb_record", "bb_policy_forward", "bb_rollout_policy",
     "bb_policy_ppo_grad", "bb_policy_ppo_grad_workspace_bytes",
+    "bb_policy_advantages", "bb_policy_advantages_workspace_bytes",
     "bb_set_action", "bb_trigger_reset", "bb_export",
     "bb_num_worlds", "bb_num_agents", "bb_exec_mode", "bb_algorithmic_bytes_per_world",
     "bb_rollout_policy_path", "bb_rollout_policy_bytes", "bb_step_staged_path", "bb_step_staged_bytes",
@@ -87,6 +88,16 @@ class PpoCoef(ctypes.Structure):
 class PolicyGrads(ctypes.Structure):
     _fields_ = [(n, ctypes.c_void_p) for n in ("w1", "b1", "ln1_w", "ln1_b", "w2", "b2", "ln2_w", "ln2_b",
                                                "head_w", "head_b")]
+
+
+class RunningStatsPtrs(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("mean", "var", "count")]
+
+
+class AdvBatch(ctypes.Structure):
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("obs", "value", "reward", "done", "next_value", "advantages",
+                                                "returns")]
+                + [("steps", ctypes.c_int64), ("worlds", ctypes.c_int64)])
 
 
 _lib = None
@@ -133,6 +144,10 @@ def load():
         "bb_policy_ppo_grad": (ctypes.c_int, [ctypes.POINTER(PolicyWeights), i32, i32, ctypes.POINTER(PpoBatch),
                                               ctypes.POINTER(PpoCoef), ctypes.POINTER(PolicyGrads), vp, vp, i64, vp]),
         "bb_policy_ppo_grad_workspace_bytes": (i64, [i64]),
+        "bb_policy_advantages": (ctypes.c_int, [i32, i32, ctypes.POINTER(AdvBatch), ctypes.POINTER(RunningStatsPtrs),
+                                                ctypes.POINTER(RunningStatsPtrs), ctypes.c_double, ctypes.c_double,
+                                                vp, vp, i64, vp]),
+        "bb_policy_advantages_workspace_bytes": (i64, [i64, i64]),
         "bb_set_action": (ctypes.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "bb_trigger_reset": (ctypes.c_int, [vp, i32, vp]),
         "bb_export": (ctypes.c_int, [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(i32),

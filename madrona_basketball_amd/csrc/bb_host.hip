@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/madrona_basketball_amd.h"
+#include "bb_advantages.h"
 #include "bb_launch.h"
 #include "bb_policy_grad.h"
 #include "bb_sim.h"
@@ -976,6 +977,60 @@ int bb_policy_ppo_grad(const bb_policy_weights *w, int32_t exec_mode, int32_t gp
     DeviceGuard g(gpu_id);
     hipError_t e = bb::launch_ppo_grad(a, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "launch PPO gradient kernels");
+    return BB_OK;
+}
+
+int64_t bb_policy_advantages_workspace_bytes(int64_t steps, int64_t worlds)
+{
+    if (steps < 1 || worlds < 1 || steps > bb::ADV_MAX_STEPS || worlds > bb::ADV_MAX_WORLDS) return 0;
+    return bb::advantages_workspace_bytes((int32_t)steps, worlds);
+}
+
+int bb_policy_advantages(int32_t exec_mode, int32_t gpu_id, const bb_adv_batch *batch,
+                         const bb_running_stats *value_norm, const bb_running_stats *obs_norm, double gamma,
+                         double gae_lambda, float *out4, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!batch || !value_norm || !obs_norm || !out4)
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: a NULL argument");
+    const void *f32[] = {batch->obs, batch->value, batch->reward, batch->done, batch->next_value, batch->advantages,
+                         batch->returns, out4};
+    for (const void *ptr : f32) {
+        if (!ptr) return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: a batch or output pointer is NULL");
+        if (((uintptr_t)ptr) & 3u) return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: a misaligned pointer");
+    }
+    if (((uintptr_t)batch->obs) & 15u)
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: obs must be 16-byte aligned");
+    const void *f64[] = {value_norm->mean, value_norm->var, value_norm->count, obs_norm->mean, obs_norm->var,
+                         obs_norm->count};
+    for (const void *ptr : f64) {
+        if (!ptr) return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: a normaliser's mean, var or count is NULL");
+        if (((uintptr_t)ptr) & 7u)
+            return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: the normalisers' doubles must be 8-byte aligned");
+    }
+    if (batch->steps < 1 || batch->worlds < 1 || batch->steps > bb::ADV_MAX_STEPS ||
+        batch->worlds > bb::ADV_MAX_WORLDS || batch->steps * batch->worlds < 2)
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: steps x worlds must be at least 2 (the unbiased "
+                                        "variance of one row is undefined)");
+    bb::AdvArgs a{};
+    a.obs = batch->obs; a.value = batch->value; a.reward = batch->reward; a.done = batch->done;
+    a.next_value = batch->next_value; a.adv = batch->advantages; a.ret = batch->returns;
+    a.vn = bb::RunStats{value_norm->mean, value_norm->var, value_norm->count};
+    a.on = bb::RunStats{obs_norm->mean, obs_norm->var, obs_norm->count};
+    a.gamma = (float)gamma; a.gl = (float)(gamma * gae_lambda);
+    a.steps = (int32_t)batch->steps; a.worlds = batch->worlds; a.out4 = out4;
+    if (exec_mode == BB_EXEC_CPU) {
+        bb::host_advantages(a);
+        return BB_OK;
+    }
+    if (exec_mode != BB_EXEC_CUDA) return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: exec_mode");
+    if (!workspace || (((uintptr_t)workspace) & 15u) ||
+        workspace_bytes < bb::advantages_workspace_bytes(a.steps, a.worlds))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: the workspace is NULL, misaligned or smaller than "
+                                        "bb_policy_advantages_workspace_bytes(steps, worlds)");
+    a.ws = (double *)workspace;
+    DeviceGuard g(gpu_id);
+    hipError_t e = bb::launch_advantages(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "launch advantage kernels");
     return BB_OK;
 }
 

@@ -198,6 +198,11 @@ struct PpoGradArgs;
 hipError_t launch_ppo_grad(const PpoGradArgs &a, hipStream_t s);
 void host_ppo_grad(const PpoGradArgs &a);
 int64_t ppo_grad_workspace_bytes(int64_t m);
+// GAE, normaliser updates and advantage normalisation (bb_advantages.h / bb_advantages.hip)
+struct AdvArgs;
+hipError_t launch_advantages(const AdvArgs &a, hipStream_t s);
+void host_advantages(const AdvArgs &a);
+int64_t advantages_workspace_bytes(int32_t steps, int64_t worlds);
 hipError_t launch_record(const RecordArgs &a, int64_t world0, int32_t count, uint32_t *dst, hipStream_t s);
 void host_record(const RecordArgs &a, int64_t world0, int32_t count, uint32_t *dst);
 // diagnostics: the step's scalar math on the device (bb_diag_math)

@@ -32,6 +32,17 @@ class _ObsNorm(torch.nn.Module):
         self.register_buffer("var", torch.ones(dim, dtype=torch.float64))
 
 
+class RunningStats:
+    """RunningMeanStd's three buffers (scripts/agent.py:24-26) at their initial
+    values -- float64 mean 0 [dim], var 1 [dim], count 1 [] -- for
+    FusedPolicy.compute_advantages to update in place."""
+
+    def __init__(self, dim: int, device=None):
+        self.mean = torch.zeros(dim, dtype=torch.float64, device=device)
+        self.var = torch.ones(dim, dtype=torch.float64, device=device)
+        self.count = torch.ones((), dtype=torch.float64, device=device)
+
+
 def make_agent(seed: int = 0) -> torch.nn.Module:
     """A torch module with the reference Agent's layout and initialisation
     (scripts/agent.py:97-131: Kaiming-normal backbone, orthogonal heads at gain
@@ -245,6 +256,69 @@ class FusedPolicy:
         a.actor.bias.grad.copy_(hb[:LOGITS])
         a.critic.bias.grad.copy_(hb[LOGITS:LOGITS + 1])
         return loss4
+
+    # --------------------------------------------------------- PPO advantages
+    def compute_advantages(self, buffers: dict, advantages: torch.Tensor, returns: torch.Tensor, value_norm,
+                           obs_norm=None, gamma: float = 0.998, gae_lambda: float = 0.95) -> torch.Tensor:
+        """compute_advantages (scripts/ppo.py:144-177) on the device,
+        bb_policy_advantages: from the buffers rollout() filled (obs [K, W, 128],
+        value / reward / done [K, W], next_value [W]) the GAE recursion on the
+        un-normalised values (agent.py:31-34 with clamp 5; the last step's
+        non-terminal flag is 1 - done[K-1], as ppo.py:157 has it), then
+        obs_norm.update(obs rows), value_norm.update(values),
+        value_norm.update(returns) in this order (agent.py:41-50, the float64
+        buffers updated in place), then advantages [K, W] = (A - mean) / (std +
+        1e-8) and returns [K, W] = the updated value_norm's clamped normalisation
+        of A + values.  value_norm / obs_norm: any objects with float64 tensors
+        mean [dim], var [dim], count [] on the policy's device (dim 1 / 128; a
+        RunningMeanStd, a RunningStats); obs_norm=None: the agent's own.
+        buffers["value"] is left as it is: ppo.py:175's `values[:] = ...` writes
+        to a temporary, and ppo_grad() takes the policy's own normalised values.
+        The packed weights still hold the old observation statistics: call
+        refresh() afterwards, as after an optimizer step.  Returns a float32 [4]
+        tensor on the device: mean and unbiased std of A before normalisation,
+        value_norm's new mean and var (no host synchronisation; torch's current
+        stream)."""
+        dev, f32, f64 = self.device, torch.float32, torch.float64
+        obs = buffers.get("obs")
+        if (obs is None or obs.dim() != 3 or obs.shape[2] != IN or obs.dtype != f32 or not obs.is_contiguous()
+                or obs.device != dev):
+            raise ValueError("buffers['obs'] must be a contiguous float32 [K, W, 128] tensor on the policy's device")
+        K, W = obs.shape[0], obs.shape[1]
+        if K * W < 2:
+            raise ValueError("compute_advantages needs at least 2 rows (the unbiased variance of one is undefined)")
+        named = {k: buffers.get(k) for k in ("value", "reward", "done")}
+        named.update(advantages=advantages, returns=returns)
+        for k, t in named.items():
+            if t is None or tuple(t.shape) != (K, W) or t.dtype != f32 or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"{k} must be a contiguous float32 [{K}, {W}] tensor on the policy's device")
+        nv = buffers.get("next_value")
+        if nv is None or tuple(nv.shape) != (W,) or nv.dtype != f32 or not nv.is_contiguous() or nv.device != dev:
+            raise ValueError(f"buffers['next_value'] must be a contiguous float32 [{W}] tensor on the policy's device")
+        if obs_norm is None:
+            obs_norm = self.agent.obs_norm
+        stats = []
+        for name, norm, dim in (("value_norm", value_norm, 1), ("obs_norm", obs_norm, IN)):
+            for field, shape in (("mean", (dim,)), ("var", (dim,)), ("count", ())):
+                t = getattr(norm, field, None)
+                if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != f64
+                        or not t.is_contiguous() or t.device != dev):
+                    raise ValueError(f"{name}.{field} must be a float64 {shape} tensor on the policy's device")
+            stats.append(_lib.RunningStatsPtrs(norm.mean.data_ptr(), norm.var.data_ptr(), norm.count.data_ptr()))
+        lib = _lib.load()
+        cuda = dev.type == "cuda"
+        need = lib.bb_policy_advantages_workspace_bytes(K, W) if cuda else 0
+        if getattr(self, "_adv_ws", None) is None or self._adv_ws.numel() * 8 < need:
+            self._adv_ws = torch.empty((max(need, 8) // 8,), dtype=f64, device=dev)
+        out4 = torch.empty((4,), dtype=f32, device=dev)
+        batch = _lib.AdvBatch(obs.data_ptr(), named["value"].data_ptr(), named["reward"].data_ptr(),
+                              named["done"].data_ptr(), nv.data_ptr(), advantages.data_ptr(), returns.data_ptr(), K, W)
+        _lib.check(lib.bb_policy_advantages(
+            int(ExecMode.CUDA if cuda else ExecMode.CPU), dev.index if dev.index is not None else -1,
+            ctypes.byref(batch), ctypes.byref(stats[0]), ctypes.byref(stats[1]), float(gamma), float(gae_lambda),
+            ctypes.c_void_p(out4.data_ptr()), ctypes.c_void_p(self._adv_ws.data_ptr() if cuda else None), need,
+            self._stream()), "policy_advantages")
+        return out4
 
     # ------------------------------------------------------------ PPO rollout
     ROLLOUT_KEYS = ("obs", "actions", "log_prob", "value", "reward", "done", "next_value")
