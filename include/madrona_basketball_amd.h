@@ -365,6 +365,56 @@ int bb_policy_advantages(int32_t exec_mode, int32_t gpu_id, const bb_adv_batch *
                          double gae_lambda, float *out4, void *workspace, int64_t workspace_bytes, void *stream);
 int64_t bb_policy_advantages_workspace_bytes(int64_t steps, int64_t worlds);
 
+/* What follows loss.backward() in one minibatch of update_policy
+ * (scripts/ppo.py:214-215): torch.nn.utils.clip_grad_norm_, then
+ * torch.optim.Adam's step with its defaults (no weight decay, no amsgrad),
+ * then the new parameters into the packed weight image `w`, so that the next
+ * bb_policy_ppo_grad / bb_policy_forward reads them.  Over all 5 972 elements:
+ *   norm = |g|_2,  coef = min(1, max_grad_norm / (norm + 1e-6)),  g = g coef
+ *   m = m + (1 - beta1)(g - m),  v = beta2 v + (1 - beta2) g g
+ *   p = p - lr / (1 - beta1^t) m / (sqrt(v) / sqrt(1 - beta2^t) + eps),  t = ++step
+ * bb_policy_params: 12 float tensors in the order of Agent.parameters()
+ * (`params`: the parameters, updated; `grads`: their .grad tensors, left
+ * clipped as clip_grad_norm_ leaves them).  Packed rows: head_w rows 0-18 =
+ * actor_w, row 19 = critic_w, rows 20-31 untouched (zero); likewise head_b.
+ * A packed pointer may equal the parameter's pointer.  obs_mean / obs_inv are
+ * not written.  bb_adam_state: exp_avg / exp_avg_sq float [5972] in the order
+ * w1 b1 ln1_w ln1_b w2 b2 ln2_w ln2_b actor_w critic_w actor_b critic_b,
+ * step int64 [1], ticket int32 [1] (CUDA mode; may be NULL in CPU mode), all
+ * zero-initialised by the caller, on the device in CUDA mode; the ticket is 0
+ * again after every call.
+ *
+ * bb_policy_adam_step: after any backward that filled `grads`.  out2 = {norm
+ * before clipping, coef}.
+ * bb_policy_ppo_step: bb_policy_ppo_grad's pass over the minibatch (same batch
+ * and coef), then the step, in two launches; nothing else is written.  out6 =
+ * {loss, pg_loss, c_loss, entropy, norm, coef}.  workspace:
+ * bb_policy_ppo_step_workspace_bytes(m) bytes on the device, 16-byte aligned
+ * (CUDA mode).  The same state and inputs give the same bits, and
+ * bb_policy_ppo_step gives the bits of bb_policy_ppo_grad followed by
+ * bb_policy_adam_step.  No synchronisation. */
+typedef struct bb_policy_params {
+    float *w1, *b1, *ln1_w, *ln1_b;
+    float *w2, *b2, *ln2_w, *ln2_b;
+    float *actor_w, *actor_b, *critic_w, *critic_b;
+} bb_policy_params;
+typedef struct bb_adam_state {
+    float *exp_avg, *exp_avg_sq;
+    int64_t *step;
+    int32_t *ticket;
+} bb_adam_state;
+typedef struct bb_adam_hyper {
+    double lr, beta1, beta2, eps, max_grad_norm;
+} bb_adam_hyper;
+int bb_policy_adam_step(const bb_policy_weights *w, int32_t exec_mode, int32_t gpu_id, const bb_policy_params *params,
+                        const bb_policy_params *grads, const bb_adam_state *state, const bb_adam_hyper *hyper,
+                        float *out2, void *stream);
+int bb_policy_ppo_step(const bb_policy_weights *w, int32_t exec_mode, int32_t gpu_id, const bb_ppo_batch *batch,
+                       const bb_ppo_coef *coef, const bb_policy_params *params, const bb_policy_params *grads,
+                       const bb_adam_state *state, const bb_adam_hyper *hyper, float *out6, void *workspace,
+                       int64_t workspace_bytes, void *stream);
+int64_t bb_policy_ppo_step_workspace_bytes(int64_t m);
+
 int bb_set_action(bb_sim *sim, int32_t world_idx, int32_t agent_idx, int32_t move_speed,
                   int32_t move_angle, int32_t rotate, int32_t grab, int32_t pass,
                   int32_t shoot, void *stream);

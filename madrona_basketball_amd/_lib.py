@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "bb_record_words", "bb_record", "bb_policy_forward", "bb_rollout_policy",
     "bb_policy_ppo_grad", "bb_policy_ppo_grad_workspace_bytes",
     "bb_policy_advantages", "bb_policy_advantages_workspace_bytes",
+    "bb_policy_adam_step", "bb_policy_ppo_step", "bb_policy_ppo_step_workspace_bytes",
     "bb_set_action", "bb_trigger_reset", "bb_export",
     "bb_num_worlds", "bb_num_agents", "bb_exec_mode", "bb_algorithmic_bytes_per_world",
     "bb_rollout_policy_path", "bb_rollout_policy_bytes", "bb_step_staged_path", "bb_step_staged_bytes",
@@ -100,6 +101,20 @@ class AdvBatch(ctypes.Structure):
                 + [("steps", ctypes.c_int64), ("worlds", ctypes.c_int64)])
 
 
+class PolicyParams(ctypes.Structure):
+    """12 float tensors in agent.parameters() order (the parameters, or their .grad)."""
+    _fields_ = [(n, ctypes.c_void_p) for n in ("w1", "b1", "ln1_w", "ln1_b", "w2", "b2", "ln2_w", "ln2_b",
+                                               "actor_w", "actor_b", "critic_w", "critic_b")]
+
+
+class AdamStatePtrs(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_void_p) for n in ("exp_avg", "exp_avg_sq", "step", "ticket")]
+
+
+class AdamHyper(ctypes.Structure):
+    _fields_ = [(n, ctypes.c_double) for n in ("lr", "beta1", "beta2", "eps", "max_grad_norm")]
+
+
 _lib = None
 
 
@@ -148,6 +163,14 @@ def load():
                                                 ctypes.POINTER(RunningStatsPtrs), ctypes.c_double, ctypes.c_double,
                                                 vp, vp, i64, vp]),
         "bb_policy_advantages_workspace_bytes": (i64, [i64, i64]),
+        "bb_policy_adam_step": (ctypes.c_int, [ctypes.POINTER(PolicyWeights), i32, i32, ctypes.POINTER(PolicyParams),
+                                               ctypes.POINTER(PolicyParams), ctypes.POINTER(AdamStatePtrs),
+                                               ctypes.POINTER(AdamHyper), vp, vp]),
+        "bb_policy_ppo_step": (ctypes.c_int, [ctypes.POINTER(PolicyWeights), i32, i32, ctypes.POINTER(PpoBatch),
+                                              ctypes.POINTER(PpoCoef), ctypes.POINTER(PolicyParams),
+                                              ctypes.POINTER(PolicyParams), ctypes.POINTER(AdamStatePtrs),
+                                              ctypes.POINTER(AdamHyper), vp, vp, i64, vp]),
+        "bb_policy_ppo_step_workspace_bytes": (i64, [i64]),
         "bb_set_action": (ctypes.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "bb_trigger_reset": (ctypes.c_int, [vp, i32, vp]),
         "bb_export": (ctypes.c_int, [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(i32),
@@ -189,6 +212,7 @@ DIAG_KEYS = {
     "ppo_step_loop": 7,              # 0: one k_step_ppo launch per step
     "policy_wg": 8,                  # k_policy_wg: 0 never, 1 always
     "ppo_opp_waves": 9,              # k_rollout_selfplay's opponent waves: 1 or 2
+    "ppo_step_ticket": 10,           # 1: bb_policy_ppo_step finishes in k_ppo_step's last workgroup (ticket)
 }
 
 

@@ -25,6 +25,7 @@
 #include "bb_advantages.h"
 #include "bb_launch.h"
 #include "bb_policy_grad.h"
+#include "bb_policy_step.h"
 #include "bb_sim.h"
 
 namespace {
@@ -505,6 +506,30 @@ int host_random_actions(int n, const Params &p, HostPool &pool, uint32_t seed, u
                 random_action(seed, step, (uint32_t)(p.world_offset + w), (uint32_t)a, p.c.action + (w * n + a) * 6);
     });
     return BB_OK;
+}
+
+// Gradient clipping, Adam's step and the repack on the host (bb_policy_step.h):
+// the raw gradient is read from the 12 .grad tensors, the norm kept in double.
+// fused: norm and coef go behind the four losses in a.out.
+void host_policy_step(const PolicyStepArgs &a, bool fused)
+{
+    double sum = 0.0;
+    for (int s = 0; s < PS_TENSORS; s++) {
+        const StepSeg sg = step_seg(a, s);
+        for (int i = 0; i < sg.len; i++) sum += (double)sg.grad[i] * (double)sg.grad[i];
+    }
+    const int64_t t = *a.step + 1;
+    *a.step = t;
+    const AdamScalars sc = adam_scalars(a.h, sum, t);
+    for (int s = 0; s < PS_TENSORS; s++) {
+        const StepSeg sg = step_seg(a, s);
+        for (int i = 0; i < sg.len; i++) {
+            sg.grad[i] = adam_element(sc, sg.grad[i], a.exp_avg + sg.e0 + i, a.exp_avg_sq + sg.e0 + i, sg.param + i);
+            sg.packed[i] = sg.param[i];
+        }
+    }
+    a.out[fused ? 4 : 0] = sc.norm;
+    a.out[fused ? 5 : 1] = sc.coef;
 }
 
 }  // namespace bb
@@ -1031,6 +1056,123 @@ int bb_policy_advantages(int32_t exec_mode, int32_t gpu_id, const bb_adv_batch *
     DeviceGuard g(gpu_id);
     hipError_t e = bb::launch_advantages(a, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "launch advantage kernels");
+    return BB_OK;
+}
+
+namespace {
+
+// The checks bb_policy_adam_step and bb_policy_ppo_step share; fills *a (all
+// but out and the fused path's workspace pointers).
+int policy_step_args(const char *who, const bb_policy_weights *w, int32_t exec_mode, const bb_policy_params *params,
+                     const bb_policy_params *grads, const bb_adam_state *state, const bb_adam_hyper *hyper,
+                     bb::PolicyStepArgs *a)
+{
+    const std::string me(who);
+    if (!w || !params || !grads || !state || !hyper) return fail(BB_ERR_INVALID_ARG, me + ": a NULL argument");
+    if (exec_mode != BB_EXEC_CPU && exec_mode != BB_EXEC_CUDA) return fail(BB_ERR_INVALID_ARG, me + ": exec_mode");
+    float *const p[bb::PS_TENSORS] = {params->w1, params->b1, params->ln1_w, params->ln1_b, params->w2, params->b2,
+                                      params->ln2_w, params->ln2_b, params->actor_w, params->actor_b, params->critic_w,
+                                      params->critic_b};
+    float *const g[bb::PS_TENSORS] = {grads->w1, grads->b1, grads->ln1_w, grads->ln1_b, grads->w2, grads->b2,
+                                      grads->ln2_w, grads->ln2_b, grads->actor_w, grads->actor_b, grads->critic_w,
+                                      grads->critic_b};
+    const void *f32[] = {w->obs_mean, w->obs_inv, w->w1, w->b1, w->ln1_w, w->ln1_b, w->w2, w->b2, w->ln2_w, w->ln2_b,
+                         w->head_w, w->head_b, state->exp_avg, state->exp_avg_sq};
+    for (int i = 0; i < 2 * bb::PS_TENSORS + 14; i++) {
+        const void *ptr = i < bb::PS_TENSORS ? p[i] : i < 2 * bb::PS_TENSORS ? g[i - bb::PS_TENSORS] : f32[i - 2 * bb::PS_TENSORS];
+        if (!ptr) return fail(BB_ERR_INVALID_ARG, me + ": a weight, parameter, gradient or state pointer is NULL");
+        if (((uintptr_t)ptr) & 3u) return fail(BB_ERR_INVALID_ARG, me + ": a misaligned pointer");
+    }
+    if (!state->step || (((uintptr_t)state->step) & 7u))
+        return fail(BB_ERR_INVALID_ARG, me + ": state->step is NULL or not 8-byte aligned");
+    if (exec_mode == BB_EXEC_CUDA && (!state->ticket || (((uintptr_t)state->ticket) & 3u)))
+        return fail(BB_ERR_INVALID_ARG, me + ": state->ticket is NULL or misaligned");
+    if (!(hyper->lr > 0.0) || !(hyper->beta1 >= 0.0 && hyper->beta1 < 1.0) || !(hyper->beta2 >= 0.0 && hyper->beta2 < 1.0) ||
+        !(hyper->eps >= 0.0) || !(hyper->max_grad_norm > 0.0))
+        return fail(BB_ERR_INVALID_ARG, me + ": lr and max_grad_norm must be positive, the betas in [0, 1), eps >= 0");
+    for (int i = 0; i < bb::PS_TENSORS; i++) {
+        a->param[i] = p[i];
+        a->grad[i] = g[i];
+    }
+    a->w = bb::PolicyWeights{w->obs_mean, w->obs_inv, w->w1, w->b1, w->ln1_w, w->ln1_b,
+                             w->w2, w->b2, w->ln2_w, w->ln2_b, w->head_w, w->head_b};
+    a->exp_avg = state->exp_avg; a->exp_avg_sq = state->exp_avg_sq; a->step = state->step; a->ticket = state->ticket;
+    a->h = bb::AdamHyper{hyper->lr, hyper->beta1, hyper->beta2, hyper->eps, hyper->max_grad_norm};
+    return BB_OK;
+}
+
+}  // namespace
+
+int bb_policy_adam_step(const bb_policy_weights *w, int32_t exec_mode, int32_t gpu_id, const bb_policy_params *params,
+                        const bb_policy_params *grads, const bb_adam_state *state, const bb_adam_hyper *hyper,
+                        float *out2, void *stream)
+{
+    bb::PolicyStepArgs a{};
+    const int rc = policy_step_args("bb_policy_adam_step", w, exec_mode, params, grads, state, hyper, &a);
+    if (rc != BB_OK) return rc;
+    if (!out2 || (((uintptr_t)out2) & 3u)) return fail(BB_ERR_INVALID_ARG, "bb_policy_adam_step: out2 is NULL or misaligned");
+    a.out = out2;
+    if (exec_mode == BB_EXEC_CPU) {
+        bb::host_policy_step(a, false);
+        return BB_OK;
+    }
+    DeviceGuard g(gpu_id);
+    hipError_t e = bb::launch_adam_step(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "launch Adam step kernel");
+    return BB_OK;
+}
+
+int64_t bb_policy_ppo_step_workspace_bytes(int64_t m)
+{
+    return m > 0 ? bb::ppo_step_workspace_bytes(m) : 0;
+}
+
+int bb_policy_ppo_step(const bb_policy_weights *w, int32_t exec_mode, int32_t gpu_id, const bb_ppo_batch *batch,
+                       const bb_ppo_coef *coef, const bb_policy_params *params, const bb_policy_params *grads,
+                       const bb_adam_state *state, const bb_adam_hyper *hyper, float *out6, void *workspace,
+                       int64_t workspace_bytes, void *stream)
+{
+    bb::PolicyStepArgs a{};
+    const int rc = policy_step_args("bb_policy_ppo_step", w, exec_mode, params, grads, state, hyper, &a);
+    if (rc != BB_OK) return rc;
+    if (!batch || !coef || !out6 || (((uintptr_t)out6) & 3u))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step: batch, coef or out6 is NULL or misaligned");
+    const void *req[] = {batch->obs, batch->actions, batch->log_prob, batch->value, batch->advantages, batch->returns};
+    for (const void *ptr : req) {
+        if (!ptr) return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step: a batch pointer is NULL");
+        if (((uintptr_t)ptr) & 3u) return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step: a misaligned pointer");
+    }
+    if ((((uintptr_t)batch->obs) & 15u) || (((uintptr_t)w->w1) & 15u) || (((uintptr_t)w->w2) & 15u) ||
+        (((uintptr_t)w->head_w) & 15u) || (((uintptr_t)batch->idx) & 7u))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step: obs and the weight matrices must be 16-byte aligned, "
+                                        "idx 8-byte aligned");
+    if (batch->rows <= 0 || batch->m <= 0 || (!batch->idx && batch->m > batch->rows))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step: rows and m must be positive (m <= rows without idx)");
+    bb::PpoGradArgs ga{};
+    ga.w = a.w;
+    ga.obs = batch->obs; ga.actions = batch->actions; ga.log_prob = batch->log_prob; ga.value = batch->value;
+    ga.adv = batch->advantages; ga.ret = batch->returns; ga.idx = batch->idx; ga.rows = batch->rows; ga.m = batch->m;
+    ga.clip = coef->clip_coef; ga.vf_coef = coef->vf_coef; ga.ent_coef = coef->ent_coef;
+    a.out = out6;
+    if (exec_mode == BB_EXEC_CPU) {
+        // host_ppo_grad's packed head gradient, then its rows into the actor's and the critic's tensors
+        float hw[bb::POL_HEAD * bb::POL_HID], hb[bb::POL_HEAD];
+        ga.g = bb::PolicyGrads{a.grad[0], a.grad[1], a.grad[2], a.grad[3], a.grad[4], a.grad[5], a.grad[6], a.grad[7], hw, hb};
+        ga.loss4 = out6;
+        bb::host_ppo_grad(ga);
+        std::memcpy(a.grad[8], hw, sizeof(float) * bb::POL_LOGITS * bb::POL_HID);
+        std::memcpy(a.grad[10], hw + bb::POL_LOGITS * bb::POL_HID, sizeof(float) * bb::POL_HID);
+        std::memcpy(a.grad[9], hb, sizeof(float) * bb::POL_LOGITS);
+        a.grad[11][0] = hb[bb::POL_LOGITS];
+        bb::host_policy_step(a, true);
+        return BB_OK;
+    }
+    if (!workspace || (((uintptr_t)workspace) & 15u) || workspace_bytes < bb::ppo_step_workspace_bytes(batch->m))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step: the workspace is NULL, misaligned or smaller than "
+                                        "bb_policy_ppo_step_workspace_bytes(m)");
+    DeviceGuard g(gpu_id);
+    hipError_t e = bb::launch_ppo_step(ga, a, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "launch PPO step kernels");
     return BB_OK;
 }
 

@@ -121,7 +121,8 @@ enum DiagKey : int {
     DIAG_PPO_STEP_LOOP = 7,              // 0: one k_step_ppo launch per step instead of one k_rollout_ppo
     DIAG_POLICY_WG = 8,                  // k_policy_wg: 0 never, 1 always (else from 98 304 rows)
     DIAG_PPO_OPP_WAVES = 9,              // k_rollout_selfplay's opponent waves: 1 or 2 (2 only at one workgroup per CU)
-    DIAG_KEYS = 10
+    DIAG_PPO_STEP_TICKET = 10,           // 1: bb_policy_ppo_step finishes in k_ppo_step's last workgroup (ticket) instead of k_adam_step
+    DIAG_KEYS = 11
 };
 extern int diag_override[DIAG_KEYS];
 inline int diag_or(int key, int dflt)
@@ -198,6 +199,14 @@ struct PpoGradArgs;
 hipError_t launch_ppo_grad(const PpoGradArgs &a, hipStream_t s);
 void host_ppo_grad(const PpoGradArgs &a);
 int64_t ppo_grad_workspace_bytes(int64_t m);
+// k_ppo_grad alone: the workgroups' partials into a.partial, their number into *groups
+hipError_t launch_ppo_grad_partials(const PpoGradArgs &a, hipStream_t s, int *groups);
+// Gradient clipping, Adam's step and the weight repack (bb_policy_step.h / bb_policy_step.hip)
+struct PolicyStepArgs;
+hipError_t launch_adam_step(const PolicyStepArgs &a, hipStream_t s);
+hipError_t launch_ppo_step(PpoGradArgs g, PolicyStepArgs a, void *workspace, hipStream_t s);
+void host_policy_step(const PolicyStepArgs &a, bool fused);
+int64_t ppo_step_workspace_bytes(int64_t m);
 // GAE, normaliser updates and advantage normalisation (bb_advantages.h / bb_advantages.hip)
 struct AdvArgs;
 hipError_t launch_advantages(const AdvArgs &a, hipStream_t s);

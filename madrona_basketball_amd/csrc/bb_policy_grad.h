@@ -216,4 +216,24 @@ inline void ppo_grad_row_host(const PpoGradArgs &a, int64_t i, double *acc)
     back(d1, h1, xh1, rstd1, W.ln1_w, x, POL_IN, W.w1, PG_W1, PG_B1, PG_LN1W, PG_LN1B, nullptr);
 }
 
+#if defined(__HIPCC__)
+// Element e's sum over the workgroups' partials in a fixed tree, for a
+// workgroup of 64 elements x 4 thread rows: row t adds the partials of
+// workgroups t, t + 4, ... in order, then (c0 + c1) + (c2 + c3) through
+// chain[4][64] in LDS (one barrier).  k_ppo_grad_reduce and k_ppo_step share
+// it: the same gradient bits from either.
+__device__ __forceinline__ float pg_tree_sum(const float *partial, int groups, int e, float (*chain)[64])
+{
+    const int x = (int)threadIdx.x, t = (int)threadIdx.y;
+    float s = 0.f;
+    if (e < PG_FLOATS) {
+#pragma unroll 8
+        for (int w = t; w < groups; w += 4) s = s + partial[(int64_t)w * PG_FLOATS + e];
+    }
+    chain[t][x] = s;
+    __syncthreads();
+    return (chain[0][x] + chain[1][x]) + (chain[2][x] + chain[3][x]);
+}
+#endif
+
 }  // namespace bb

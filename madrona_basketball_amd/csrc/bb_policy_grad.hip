@@ -432,13 +432,7 @@ __global__ __launch_bounds__(256) void k_ppo_grad_reduce(const float *partial, i
 {
     __shared__ float chain[4][64];
     const int e = (int)(blockIdx.x * 64 + threadIdx.x), t = (int)threadIdx.y;
-    float s = 0.f;
-    if (e < PG_FLOATS) {
-#pragma unroll 8
-        for (int w = t; w < groups; w += 4) s = s + partial[(int64_t)w * PG_FLOATS + e];
-    }
-    chain[t][threadIdx.x] = s;
-    __syncthreads();
+    const float v = pg_tree_sum(partial, groups, e, chain);
     if (t != 0) return;
     if (e >= PG_FLOATS) {
         const int k = e - PG_FLOATS;
@@ -446,8 +440,6 @@ __global__ __launch_bounds__(256) void k_ppo_grad_reduce(const float *partial, i
         else if (k < PG_HEAD_PAD) g.head_b[PG_HEAD_LIVE + (k - (POL_HEAD - PG_HEAD_LIVE) * POL_HID)] = 0.f;
         return;
     }
-    const int x = (int)threadIdx.x;
-    const float v = (chain[0][x] + chain[1][x]) + (chain[2][x] + chain[3][x]);
     if (e < PG_B1) g.w1[e] = v;
     else if (e < PG_LN1W) g.b1[e - PG_B1] = v;
     else if (e < PG_LN1B) g.ln1_w[e - PG_LN1W] = v;
@@ -482,11 +474,18 @@ int64_t ppo_grad_workspace_bytes(int64_t m)
     return (int64_t)ppo_grad_grid(m).groups * PG_FLOATS * (int64_t)sizeof(float);
 }
 
-hipError_t launch_ppo_grad(const PpoGradArgs &a, hipStream_t s)
+hipError_t launch_ppo_grad_partials(const PpoGradArgs &a, hipStream_t s, int *groups)
 {
     const PpoGradGrid gr = ppo_grad_grid(a.m);
+    *groups = gr.groups;
     hipLaunchKernelGGL(k_ppo_grad, dim3(gr.groups), dim3(64 * gr.waves), 0, s, a);
-    hipError_t e = hipGetLastError();
+    return hipGetLastError();
+}
+
+hipError_t launch_ppo_grad(const PpoGradArgs &a, hipStream_t s)
+{
+    PpoGradGrid gr;
+    hipError_t e = launch_ppo_grad_partials(a, s, &gr.groups);
     if (e != hipSuccess) return e;
     const int items = PG_FLOATS + PG_HEAD_PAD;
     hipLaunchKernelGGL(k_ppo_grad_reduce, dim3((items + 63) / 64), dim3(64, 4), 0, s, a.partial, gr.groups, a.g, a.loss4);

@@ -7,7 +7,10 @@ scripts/ppo.py:67 / scripts/env.py:147 without a round trip through torch.
 
 FusedPolicy.from_agent(agent) snapshots the weights of any torch module with
 the reference Agent's layout (obs_norm.mean/var, backbone Linear/LayerNorm,
-actor, critic); call refresh() after an optimizer step.
+actor, critic).  The packed weights follow the agent through
+optimizer_step / ppo_minibatch / ppo_update (clipping, Adam and the repack in
+one launch); after a torch optimizer step, or after compute_advantages (new
+observation statistics), call refresh().
 """
 from __future__ import annotations
 
@@ -20,6 +23,7 @@ from .madrona import ExecMode
 
 BUCKETS = (2, 8, 3, 2, 2, 2)
 IN, HID, LOGITS, HEAD = 128, 32, 19, 32
+PARAMS = HID * IN + HID * HID + 6 * HID + (LOGITS + 1) * (HID + 1)  # 5 972
 
 
 class _ObsNorm(torch.nn.Module):
@@ -85,6 +89,20 @@ def agent_from_state_dict(state_dict: dict, device=None) -> torch.nn.Module:
                 raise ValueError(f"{k}: shape {tuple(src.shape)}, expected {tuple(v.shape)}")
             v.copy_(src.to(v.dtype))
     return m if device is None else m.to(device)
+
+
+class AdamState:
+    """torch.optim.Adam's state for the agent's 5 972 parameter elements, zeroed,
+    for FusedPolicy.optimizer_step / ppo_minibatch / ppo_update: exp_avg and
+    exp_avg_sq float32 [5972] in the gradient's packed order (w1 b1 ln1_w ln1_b
+    w2 b2 ln2_w ln2_b actor.w critic.w actor.b critic.b), step int64 [1], and
+    the kernels' ticket int32 [1] (0 between calls)."""
+
+    def __init__(self, device=None):
+        self.exp_avg = torch.zeros(PARAMS, dtype=torch.float32, device=device)
+        self.exp_avg_sq = torch.zeros(PARAMS, dtype=torch.float32, device=device)
+        self.step = torch.zeros(1, dtype=torch.int64, device=device)
+        self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
 
 
 class FusedPolicy:
@@ -201,6 +219,33 @@ class FusedPolicy:
         tensor on the device: loss, pg_loss, c_loss before vf_coef, mean entropy
         (no host synchronisation).  head_grad keeps the packed head's gradient
         ([32, 32] and [32]: rows 0-18 the actor, 19 the critic, 20-31 zero)."""
+        batch, m = self._ppo_args(obs, actions, log_prob, value, advantages, returns, idx)
+        direct = self._params(True)[:8]
+        dev, f32, a = self.device, torch.float32, self.agent
+        lib = _lib.load()
+        cuda = dev.type == "cuda"
+        need = lib.bb_policy_ppo_grad_workspace_bytes(m) if cuda else 0
+        if getattr(self, "_ppo_ws", None) is None or self._ppo_ws.numel() * 4 < need:
+            self._ppo_ws = torch.empty((max(need, 4) // 4,), dtype=f32, device=dev)
+        if getattr(self, "head_grad", None) is None:
+            self.head_grad = (torch.zeros((HEAD, HID), dtype=f32, device=dev), torch.zeros((HEAD,), dtype=f32, device=dev))
+        hw, hb = self.head_grad
+        loss4 = torch.empty((4,), dtype=f32, device=dev)
+        coef = _lib.PpoCoef(float(clip_coef), float(vf_coef), float(ent_coef))
+        grads = _lib.PolicyGrads(*[p.grad.data_ptr() for p in direct], hw.data_ptr(), hb.data_ptr())
+        _lib.check(lib.bb_policy_ppo_grad(
+            ctypes.byref(self._w), int(ExecMode.CUDA if cuda else ExecMode.CPU),
+            dev.index if dev.index is not None else -1, ctypes.byref(batch), ctypes.byref(coef), ctypes.byref(grads),
+            ctypes.c_void_p(loss4.data_ptr()), ctypes.c_void_p(self._ppo_ws.data_ptr() if cuda else None),
+            need, self._stream()), "policy_ppo_grad")
+        a.actor.weight.grad.copy_(hw[:LOGITS])
+        a.critic.weight.grad.copy_(hw[LOGITS:LOGITS + 1])
+        a.actor.bias.grad.copy_(hb[:LOGITS])
+        a.critic.bias.grad.copy_(hb[LOGITS:LOGITS + 1])
+        return loss4
+
+    def _ppo_args(self, obs, actions, log_prob, value, advantages, returns, idx):
+        """ppo_grad's checks of the batch: its descriptor and M."""
         dev, f32 = self.device, torch.float32
         if obs.dim() != 2 or obs.shape[1] != IN or obs.dtype != f32 or not obs.is_contiguous():
             raise ValueError("obs must be a contiguous float32 [rows, 128] tensor")
@@ -218,44 +263,113 @@ class FusedPolicy:
         for t in (obs, actions, log_prob, value, advantages, returns, idx):
             if t is not None and t.device != dev:
                 raise ValueError("all tensors must live on the policy's device")
-        a = self.agent
-        lin = [mod for mod in a.backbone if isinstance(mod, torch.nn.Linear)]
-        lns = [mod for mod in a.backbone if isinstance(mod, torch.nn.LayerNorm)]
-        direct = [lin[0].weight, lin[0].bias, lns[0].weight, lns[0].bias,
-                  lin[1].weight, lin[1].bias, lns[1].weight, lns[1].bias]
-        heads = [a.actor.weight, a.critic.weight, a.actor.bias, a.critic.bias]
-        if tuple(direct[0].shape) != (HID, IN) or tuple(direct[4].shape) != (HID, HID) or a.actor.out_features != LOGITS:
-            raise ValueError("FusedPolicy supports the reference configuration: input 128, num_channels 32, "
-                             "num_layers 2, buckets [2, 8, 3, 2, 2, 2] (scripts/env.py:107)")
-        for p in direct + heads:
-            if p.device != dev or p.dtype != f32:
-                raise ValueError("the agent's parameters must be float32 on the policy's device")
-            if p.grad is None or not p.grad.is_contiguous():
-                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
-        lib = _lib.load()
-        cuda = dev.type == "cuda"
-        need = lib.bb_policy_ppo_grad_workspace_bytes(m) if cuda else 0
-        if getattr(self, "_ppo_ws", None) is None or self._ppo_ws.numel() * 4 < need:
-            self._ppo_ws = torch.empty((max(need, 4) // 4,), dtype=f32, device=dev)
-        if getattr(self, "head_grad", None) is None:
-            self.head_grad = (torch.zeros((HEAD, HID), dtype=f32, device=dev), torch.zeros((HEAD,), dtype=f32, device=dev))
-        hw, hb = self.head_grad
-        loss4 = torch.empty((4,), dtype=f32, device=dev)
         batch = _lib.PpoBatch(obs.data_ptr(), actions.data_ptr(), log_prob.data_ptr(), value.data_ptr(),
                               advantages.data_ptr(), returns.data_ptr(), None if idx is None else idx.data_ptr(),
                               rows, m)
+        return batch, m
+
+    def _params(self, make_grads: bool) -> list:
+        """The agent's 12 parameters in agent.parameters() order (w1 b1 ln1_w ln1_b
+        w2 b2 ln2_w ln2_b actor.w actor.b critic.w critic.b), float32 on the
+        policy's device, each with a contiguous .grad (made if make_grads)."""
+        a, dev = self.agent, self.device
+        lin = [mod for mod in a.backbone if isinstance(mod, torch.nn.Linear)]
+        lns = [mod for mod in a.backbone if isinstance(mod, torch.nn.LayerNorm)]
+        ps = [lin[0].weight, lin[0].bias, lns[0].weight, lns[0].bias, lin[1].weight, lin[1].bias, lns[1].weight,
+              lns[1].bias, a.actor.weight, a.actor.bias, a.critic.weight, a.critic.bias]
+        if tuple(ps[0].shape) != (HID, IN) or tuple(ps[4].shape) != (HID, HID) or a.actor.out_features != LOGITS:
+            raise ValueError("FusedPolicy supports the reference configuration: input 128, num_channels 32, "
+                             "num_layers 2, buckets [2, 8, 3, 2, 2, 2] (scripts/env.py:107)")
+        for p in ps:
+            if p.device != dev or p.dtype != torch.float32:
+                raise ValueError("the agent's parameters must be float32 on the policy's device")
+            if make_grads and (p.grad is None or not p.grad.is_contiguous()):
+                p.grad = torch.zeros_like(p, memory_format=torch.contiguous_format)
+            if p.grad is None or not p.grad.is_contiguous():
+                raise ValueError("every parameter needs a contiguous .grad (run a backward first)")
+        return ps
+
+    def _step_args(self, state: "AdamState", lr, max_grad_norm, betas, eps, make_grads: bool):
+        if not isinstance(state, AdamState) or state.exp_avg.device != self.device:
+            raise ValueError("state must be an AdamState on the policy's device")
+        ps = self._params(make_grads)
+        if any(not p.is_contiguous() for p in ps):
+            raise ValueError("the agent's parameters must be contiguous")
+        return (_lib.PolicyParams(*[p.data_ptr() for p in ps]), _lib.PolicyParams(*[p.grad.data_ptr() for p in ps]),
+                _lib.AdamStatePtrs(state.exp_avg.data_ptr(), state.exp_avg_sq.data_ptr(), state.step.data_ptr(),
+                                   state.ticket.data_ptr()),
+                _lib.AdamHyper(float(lr), float(betas[0]), float(betas[1]), float(eps), float(max_grad_norm)))
+
+    @torch.no_grad()
+    def optimizer_step(self, state: "AdamState", lr: float = 3e-4, max_grad_norm: float = 1.0,
+                       betas=(0.9, 0.999), eps: float = 1e-8) -> torch.Tensor:
+        """clip_grad_norm_(agent.parameters(), max_grad_norm) + Adam.step() +
+        refresh() (scripts/ppo.py:214-215) after any backward, in one launch,
+        bb_policy_adam_step: the 12 .grad tensors are left clipped, `state` and the
+        parameters take torch.optim.Adam's step (defaults: no weight decay, no
+        amsgrad), and the new parameters are stored into the packed weights too
+        (the observation statistics are not: refresh() after compute_advantages
+        as before).  Returns float32 [2] on the device: the gradient norm before
+        clipping and the clip factor (no host synchronisation)."""
+        params, grads, st, hyper = self._step_args(state, lr, max_grad_norm, betas, eps, False)
+        dev = self.device
+        out2 = torch.empty((2,), dtype=torch.float32, device=dev)
+        _lib.check(_lib.load().bb_policy_adam_step(
+            ctypes.byref(self._w), int(ExecMode.CUDA if dev.type == "cuda" else ExecMode.CPU),
+            dev.index if dev.index is not None else -1, ctypes.byref(params), ctypes.byref(grads), ctypes.byref(st),
+            ctypes.byref(hyper), ctypes.c_void_p(out2.data_ptr()), self._stream()), "policy_adam_step")
+        return out2
+
+    @torch.no_grad()
+    def ppo_minibatch(self, obs: torch.Tensor, actions: torch.Tensor, log_prob: torch.Tensor, value: torch.Tensor,
+                      advantages: torch.Tensor, returns: torch.Tensor, idx: torch.Tensor, state: "AdamState",
+                      clip_coef: float = 0.2, vf_coef: float = 1.0, ent_coef: float = 0.01, lr: float = 3e-4,
+                      max_grad_norm: float = 1.0, betas=(0.9, 0.999), eps: float = 1e-8) -> torch.Tensor:
+        """One whole minibatch of update_policy (scripts/ppo.py:190-215): ppo_grad's
+        pass (same arguments and checks), then optimizer_step's, as two launches
+        (bb_policy_ppo_step) with no torch op between them -- the bits of
+        ppo_grad() followed by optimizer_step().  Returns float32 [6] on the
+        device: loss, pg_loss, c_loss, entropy, gradient norm before clipping,
+        clip factor."""
+        batch, m = self._ppo_args(obs, actions, log_prob, value, advantages, returns, idx)
+        params, grads, st, hyper = self._step_args(state, lr, max_grad_norm, betas, eps, True)
+        dev, lib = self.device, _lib.load()
+        cuda = dev.type == "cuda"
+        need = lib.bb_policy_ppo_step_workspace_bytes(m) if cuda else 0
+        if getattr(self, "_ppo_ws", None) is None or self._ppo_ws.numel() * 4 < need:
+            self._ppo_ws = torch.empty((max(need, 4) // 4,), dtype=torch.float32, device=dev)
+        out6 = torch.empty((6,), dtype=torch.float32, device=dev)
         coef = _lib.PpoCoef(float(clip_coef), float(vf_coef), float(ent_coef))
-        grads = _lib.PolicyGrads(*[p.grad.data_ptr() for p in direct], hw.data_ptr(), hb.data_ptr())
-        _lib.check(lib.bb_policy_ppo_grad(
+        _lib.check(lib.bb_policy_ppo_step(
             ctypes.byref(self._w), int(ExecMode.CUDA if cuda else ExecMode.CPU),
-            dev.index if dev.index is not None else -1, ctypes.byref(batch), ctypes.byref(coef), ctypes.byref(grads),
-            ctypes.c_void_p(loss4.data_ptr()), ctypes.c_void_p(self._ppo_ws.data_ptr() if cuda else None),
-            need, self._stream()), "policy_ppo_grad")
-        a.actor.weight.grad.copy_(hw[:LOGITS])
-        a.critic.weight.grad.copy_(hw[LOGITS:LOGITS + 1])
-        a.actor.bias.grad.copy_(hb[:LOGITS])
-        a.critic.bias.grad.copy_(hb[LOGITS:LOGITS + 1])
-        return loss4
+            dev.index if dev.index is not None else -1, ctypes.byref(batch), ctypes.byref(coef), ctypes.byref(params),
+            ctypes.byref(grads), ctypes.byref(st), ctypes.byref(hyper), ctypes.c_void_p(out6.data_ptr()),
+            ctypes.c_void_p(self._ppo_ws.data_ptr() if cuda else None), need, self._stream()), "policy_ppo_step")
+        return out6
+
+    def ppo_update(self, obs: torch.Tensor, actions: torch.Tensor, log_prob: torch.Tensor, value: torch.Tensor,
+                   advantages: torch.Tensor, returns: torch.Tensor, state: "AdamState", update_epochs: int = 4,
+                   num_minibatches: int = 4, perms: torch.Tensor = None, **kw) -> torch.Tensor:
+        """update_policy (scripts/ppo.py:180-216) over the flat buffer views of
+        ppo_grad: per epoch a permutation of the R rows (row e of `perms`, int64
+        [update_epochs, R], or torch.randperm on the device), minibatches of
+        R // num_minibatches rows at range(0, R, minibatch_size) -- a short last
+        one when R is not divisible, as ppo.py:188 has it -- each one
+        ppo_minibatch(**kw).  Returns float32 [steps, 6], one row per minibatch."""
+        rows = obs.shape[0]
+        mb = rows // int(num_minibatches)
+        if mb < 1:
+            raise ValueError("fewer rows than minibatches")
+        if perms is not None and (tuple(perms.shape) != (update_epochs, rows) or perms.dtype != torch.int64
+                                  or perms.device != self.device or not perms.is_contiguous()):
+            raise ValueError("perms must be a contiguous int64 [update_epochs, R] tensor on the policy's device")
+        out = []
+        for e in range(int(update_epochs)):
+            b_inds = perms[e] if perms is not None else torch.randperm(rows, device=self.device)
+            for start in range(0, rows, mb):
+                out.append(self.ppo_minibatch(obs, actions, log_prob, value, advantages, returns,
+                                              b_inds[start:start + mb], state, **kw))
+        return torch.stack(out)
 
     # --------------------------------------------------------- PPO advantages
     def compute_advantages(self, buffers: dict, advantages: torch.Tensor, returns: torch.Tensor, value_norm,
