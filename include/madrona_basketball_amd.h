@@ -262,11 +262,13 @@ int bb_policy_forward(const bb_policy_weights *w, int32_t exec_mode, int32_t gpu
  * (bb_policy_forward on the trainee rows; bb_step) with the reads above.
  * On gfx950, up to 16 384 worlds one fused launch runs all n steps with the
  * worlds in registers (BB_PPO_PATH_FUSED_ROLLOUT), the opponent's network too
- * when there is one; above, without an opponent, a policy launch and then one
- * launch in which every wave runs its worlds' n steps, each followed by the
- * next policy pass on the rows in LDS (BB_PPO_PATH_FUSED_STEP).  flags
+ * when there is one; above, one launch in which every wave runs the policy
+ * pass of step 0 and then its worlds' n steps, each followed by the next
+ * policy pass on the rows in LDS (BB_PPO_PATH_FUSED_STEP) -- with an opponent
+ * the frozen network's pass too, on the other agent's rows in the same LDS
+ * tile, so an opponent runs in the one launch at every world count.  flags
  * BB_ROLLOUT_PER_STEP forces a policy launch (two with an opponent) and a step
- * launch per step instead (so does an opponent above 16 384 worlds); from 32 768
+ * launch per step instead; from 32 768
  * worlds those per-step launches of two world halves go to `stream` and to a
  * second stream the simulator owns (created on first use, destroyed by
  * bb_destroy); `stream` waits for both before the call's last work, so stream
@@ -288,7 +290,7 @@ int bb_rollout_policy(bb_sim *sim, const bb_policy_weights *w, const bb_policy_w
  * bb_last_error() says why. */
 #define BB_PPO_PATH_HOST 0          /* CPU mode: the host executor */
 #define BB_PPO_PATH_FUSED_ROLLOUT 1 /* one k_rollout_policy (opponent: k_rollout_selfplay) launch for all n steps */
-#define BB_PPO_PATH_FUSED_STEP 2    /* a policy launch, then k_rollout_ppo (step + next policy pass, n times) */
+#define BB_PPO_PATH_FUSED_STEP 2    /* one k_rollout_ppo launch: policy pass 0, then n x (step + next policy pass; opponent: both networks' passes) */
 #define BB_PPO_PATH_PER_STEP 3      /* a policy launch and a step launch per step */
 int32_t bb_rollout_policy_path(const bb_sim *sim, int32_t with_opponent, uint32_t flags);
 int64_t bb_rollout_policy_bytes(const bb_sim *sim, int32_t with_opponent, uint32_t flags, int32_t n);

@@ -213,6 +213,7 @@ DIAG_KEYS = {
     "policy_wg": 8,                  # k_policy_wg: 0 never, 1 always
     "ppo_opp_waves": 9,              # k_rollout_selfplay's opponent waves: 1 or 2
     "ppo_step_ticket": 10,           # 1: bb_policy_ppo_step finishes in k_ppo_step's last workgroup (ticket)
+    "ppo_selfplay_step_min_worlds": 11,  # with an opponent: the fused PPO step from this many worlds (0: never)
 }
 
 

@@ -7,7 +7,7 @@
 
 namespace bb {
 
-int diag_override[DIAG_KEYS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
+int diag_override[DIAG_KEYS] = {-1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1, -1};
 
 // one lane = one (world, agent) action row (24 B); N compile-time so the
 // row -> (world, agent) split is a multiply, not a 64-bit division

@@ -1267,6 +1267,21 @@ static bool ppo_step_loop() { return bb::diag_or(bb::DIAG_PPO_STEP_LOOP, 1) != 0
 // DIAG_PPO_STEP_FUSED_MIN_WORLDS overrides it (0: never; tests).
 static int64_t ppo_step_fused_min_worlds() { return bb::diag_or(bb::DIAG_PPO_STEP_FUSED_MIN_WORLDS, 1); }
 
+// With a frozen opponent the fused step is k_rollout_ppo's self-play form (the
+// opponent's network on the other agent's rows, which the wave's tile holds
+// anyway), from this many worlds on, wherever the fused rollout is not taken
+// and the steps run in one launch (k_step_ppo has no opponent form).
+// Measured per step, K = 32, all records, against the per-step launches:
+// 24 576 worlds 25.8 vs 45.1 us, 32 768 26.0 vs 49.2, 65 536 51.1 vs 71.0
+// (profiles/r11/selfplay_step_ab.txt): ahead from the first count above the
+// fused rollout's bound, so from 16 385.
+// DIAG_PPO_SELFPLAY_STEP_MIN_WORLDS overrides it (0: never; tests, A/B timing).
+constexpr int PPO_SELFPLAY_STEP_MIN_WORLDS = 16385;
+static int64_t ppo_selfplay_step_min_worlds()
+{
+    return bb::diag_or(bb::DIAG_PPO_SELFPLAY_STEP_MIN_WORLDS, PPO_SELFPLAY_STEP_MIN_WORLDS);
+}
+
 // The implementation bb_rollout_policy takes (BB_PPO_PATH_*).
 static int32_t ppo_path(const bb_sim *s, bool opponent, uint32_t flags)
 {
@@ -1275,12 +1290,14 @@ static int32_t ppo_path(const bb_sim *s, bool opponent, uint32_t flags)
     const int64_t W = s->cfg.num_worlds;
     // with an opponent too (k_rollout_selfplay), to the same bound: measured
     // per step, K = 32, 8 192 worlds 10.5 us against 31.4 for the per-step
-    // launches, 16 384 worlds 15.4 against 37.5 (profiles/r07/selfplay_ab.txt);
-    // above the bound an opponent keeps the per-step launches
+    // launches, 16 384 worlds 15.4 against 37.5 (profiles/r07/selfplay_ab.txt)
     if (!(flags & BB_ROLLOUT_PER_STEP) && bb::fused_rollout_n(s->n) && W <= ppo_fused_max_worlds())
         return BB_PPO_PATH_FUSED_ROLLOUT;
     if (!(flags & BB_ROLLOUT_PER_STEP) && !opponent && s->n == 2 && ppo_step_fused_min_worlds() > 0 &&
         W >= ppo_step_fused_min_worlds())
+        return BB_PPO_PATH_FUSED_STEP;
+    if (!(flags & BB_ROLLOUT_PER_STEP) && opponent && s->n == 2 && ppo_step_loop() &&
+        ppo_selfplay_step_min_worlds() > 0 && W >= ppo_selfplay_step_min_worlds())
         return BB_PPO_PATH_FUSED_STEP;
     return BB_PPO_PATH_PER_STEP;
 }
@@ -1406,6 +1423,10 @@ int bb_rollout_policy(bb_sim *s, const bb_policy_weights *w, const bb_policy_wei
                 a.value = out->value ? out->value + W : nullptr;
             }
             a.value_last = out->next_value;
+            if (opponent) {
+                a.opp = policy_weights(opponent);
+                a.has_opp = 1;
+            }
             e = bb::launch_rollout_ppo(s->n, s->p, a, n, st);
         }
         for (int32_t k = 0; k < (ppo_step_loop() ? 0 : n) && e == hipSuccess; k++) {
@@ -1896,6 +1917,8 @@ int64_t bb_rollout_policy_bytes(const bb_sim *s, int32_t with_opponent, uint32_t
         // next_value.  (k_rollout_ppo also round-trips each step's state and
         // action rows through memory -- L2 hits mostly, its PMC traffic is
         // 2x these bytes -- which the fused rollout's registers avoid.)
+        // Self-play is charged the same: the opponent's rows never leave
+        // LDS, only its weights are new.
         return B + rec + (int64_t)n * (rec + outs + rd) + 4;
     default:
         // per step: the world step (the trainee's row into buffer.obs[k+1]

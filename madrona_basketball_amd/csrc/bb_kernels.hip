@@ -1481,11 +1481,52 @@ constexpr int PPS_RS = 60;  // tile row stride (floats): 14 pieces + 1, == 4 mod
 #endif
 constexpr int PPS_TILE = WAVE * PPS_RS;
 
-template <int WPG>
+template <int WPG, bool OPP = false>
 struct PpoStepLds {
     PolicyLdsWeights wt;
     float tile[WPG][PPS_TILE];
 };
+// Self-play (k_rollout_ppo<WPG, true>): the frozen opponent's network beside
+// the trainee's, 2 x 32.6 KB per workgroup.
+template <int WPG>
+struct PpoStepLds<WPG, true> {
+    PolicyLdsWeights wt, ow;
+    float tile[WPG][PPS_TILE];
+};
+static_assert(sizeof(PpoStepLds<6, true>) <= 160 * 1024 && sizeof(PpoStepLds<4, true>) <= 160 * 1024,
+              "the self-play workgroup's LDS");
+
+// The frozen opponent's tail on the wave's 32 rows of the other agent: from
+// its layer-1 accumulators (ppo_layer1_pass on tile rows 2m + 1 - trainee with
+// the opponent's image) LayerNorm 1, layer 2, heads and the bucket pass through
+// the tile's first 32 x 33 floats and the BucketLds behind them, as the
+// trainee's tail before it -- the operations of k_policy on those rows, always
+// sampling with the opponent's key; only the six actions leave, into the other
+// agent's rows of the sim's action column.
+__device__ __forceinline__ void ppo_opponent_tail(const Params &p, const PolicyLdsWeights &L, float *tile,
+                                                  const f32x4 (&acc)[2][2], const BucketNoise<32> &noise, int trainee,
+                                                  uint32_t seed, uint32_t step, int64_t w0, int lane)
+{
+    const int pl = lane & 15, pq = lane >> 4;
+    float (*lt)[33] = (float (*)[33])tile;
+    wave_sync();  // the trainee's bucket pass has read its rows and its exchange
+#pragma unroll
+    for (int mt = 0; mt < 2; mt++)
+        ln_relu_to_tile(acc[mt][0], acc[mt][1], L.cst[0][pl], L.cst[0][pl + 16], L.cst[1][pl], L.cst[1][pl + 16],
+                        L.cst[2][pl], L.cst[2][pl + 16], lt + 16 * mt, pl, pq);
+    pol_wave_sync();
+    policy_tail_lds2(L, lt, pl, pq);
+    PolicyArgs pa{};
+    pa.rows = p.num_worlds;
+    pa.stochastic = 1;
+    pa.seed = seed;
+    pa.step = step;
+    pa.actions = p.c.action + (1 - trainee) * 6;
+    pa.act_stride = 2 * 6;
+    BucketLds<32> &bl = *(BucketLds<32> *)(tile + 32 * 33);
+    bucket_pass_spread<32, true, 1>(pa, lt, w0, lane, bl, nullptr, &noise);
+}
+constexpr uint32_t PPO_OPP_KEY = 0x9E3779B9u;  // the opponent's sampling key: seed ^ this (bb_rollout_policy)
 
 // Floats of pass P of a row into its tile row (compile-time indices: straight
 // float4 LDS writes of the pass's pieces, the other floats never computed).
@@ -1656,10 +1697,19 @@ __device__ __forceinline__ PpoStepArgs ppo_loop_args(const PpoStepArgs &a0, int3
 
 // LOOP: a step of k_rollout_ppo's loop (the weights are in LDS already; no
 // workgroup barrier, the waves run their worlds' steps independently).
-template <int WPG, bool LAST, bool LOOP = false>
-__device__ __forceinline__ void ppo_step_wave(const Params &p, const PpoStepArgs &a, PpoStepLds<WPG> &S, int blk,
+// OPP (self-play, LOOP only): before the last step the frozen opponent's
+// network runs too, on the other agent's rows -- tile row 2m + 1 - trainee is
+// that agent's lane's own row, in the tile with the trainee's -- its layer-1
+// chain steps behind the trainee's on each pass (a second accumulator set, the
+// opponent's normaliser and weights from its own image), its tail after the
+// trainee's; its actions go into the other agent's rows of the action column,
+// which the next step loads behind the per-step fence.
+template <int WPG, bool LAST, bool LOOP = false, bool OPP = false>
+__device__ __forceinline__ void ppo_step_wave(const Params &p, const PpoStepArgs &a, PpoStepLds<WPG, OPP> &S, int blk,
                                               int wave, int lane)
 {
+    static_assert(!OPP || LOOP, "the opponent's form is k_rollout_ppo's");
+    constexpr bool OACT = OPP && !LAST;  // the opponent acts for the next step
     constexpr int N = 2;
     float *tile = S.tile[wave];
     const int k = lane % N;
@@ -1688,6 +1738,8 @@ __device__ __forceinline__ void ppo_step_wave(const Params &p, const PpoStepArgs
     // off the bucket pass's chain
     BucketNoise<32> noise;
     if (!LAST && a.stochastic) bucket_noise<32>(noise, a.seed, a.step, w0, p.num_worlds, lane);
+    BucketNoise<32> onoise;
+    if constexpr (OACT) bucket_noise<32>(onoise, a.seed ^ PPO_OPP_KEY, a.step, w0, p.num_worlds, lane);
     // the workgroup's copy of the network (read after the barrier below)
     if (!LOOP) policy_weights_to_lds(S.wt, a.w, (int)threadIdx.x, WPG * WAVE);
     if (active) step_world_pre_obs(s, c, ag);
@@ -1718,16 +1770,23 @@ __device__ __forceinline__ void ppo_step_wave(const Params &p, const PpoStepArgs
     f32x4 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; i++) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 oacc[2][2];
+    if constexpr (OACT) {
+#pragma unroll
+        for (int i = 0; i < 2; i++) oacc[i][0] = oacc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     wave_sync();  // the parked words are read
     ppo_emit_pass<0>(v, c, sh, active, fast, share, tile + lane * PPS_RS, ib);
     if (!LOOP) lds_barrier();  // the pass's rows, and the workgroup's weights, are in LDS
     else wave_sync();
     ppo_layer1_pass<0>(tile, S.wt, acc, trainee, pl, pq);
+    if constexpr (OACT) ppo_layer1_pass<0>(tile, S.ow, oacc, 1 - trainee, pl, pq);
     ppo_flush_pass<0, LAST>(tile, obs, rec, live, trainee, lane);
     wave_sync();
     ppo_emit_pass<1>(v, c, sh, active, fast, share, tile + lane * PPS_RS, ib);
     wave_sync();
     ppo_layer1_pass<1>(tile, S.wt, acc, trainee, pl, pq);
+    if constexpr (OACT) ppo_layer1_pass<1>(tile, S.ow, oacc, 1 - trainee, pl, pq);
     ppo_flush_pass<1, LAST>(tile, obs, rec, live, trainee, lane);
     wave_sync();
     if (LAST && !a.value) return;  // (wave-uniform; no barrier follows)
@@ -1757,6 +1816,8 @@ __device__ __forceinline__ void ppo_step_wave(const Params &p, const PpoStepArgs
         if (a.stochastic) bucket_pass_spread<32, true, 1>(pa, lt, w0, lane, bl, nullptr, &noise);
         else bucket_pass_spread<32, true, 0>(pa, lt, w0, lane, bl, nullptr, &noise);
     }
+    if constexpr (OACT)
+        ppo_opponent_tail(p, S.ow, tile, oacc, onoise, trainee, a.seed ^ PPO_OPP_KEY, a.step, w0, lane);
 }
 
 // The policy pass of step 0 inside k_rollout_ppo (what a k_policy launch on
@@ -1765,9 +1826,10 @@ __device__ __forceinline__ void ppo_step_wave(const Params &p, const PpoStepArgs
 // row floats i with ((i >> 4) & 1) == P and i < 104 at slot (i >> 5) * 16 +
 // (i & 15), as PassSink leaves them), the same layer-1 chain steps, LayerNorms,
 // layers and bucket pass as after every step (bit-identical to k_policy), the
-// rows copied into buffer.obs[0].
-template <int WPG>
-__device__ __forceinline__ void ppo_pass0_wave(const Params &p, const PpoStepArgs &a, PpoStepLds<WPG> &S, int blk,
+// rows copied into buffer.obs[0].  OPP: the same for the frozen opponent on
+// the other agent's sim rows (into tile rows 2m + 1 - trainee), actions only.
+template <int WPG, bool OPP = false>
+__device__ __forceinline__ void ppo_pass0_wave(const Params &p, const PpoStepArgs &a, PpoStepLds<WPG, OPP> &S, int blk,
                                                int wave, int lane)
 {
     constexpr int N = 2, OW = obs_width(N);
@@ -1783,6 +1845,13 @@ __device__ __forceinline__ void ppo_pass0_wave(const Params &p, const PpoStepArg
     f32x4 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; i++) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    BucketNoise<32> onoise;
+    f32x4 oacc[2][2];
+    if constexpr (OPP) {
+        bucket_noise<32>(onoise, a.seed ^ PPO_OPP_KEY, a.step0, w0, W, lane);
+#pragma unroll
+        for (int i = 0; i < 2; i++) oacc[i][0] = oacc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     const auto pass = [&](auto pc) {
         constexpr int P = decltype(pc)::value;
         constexpr int NPC = P == 0 ? 14 : 12;  // float4 pieces of the pass per row
@@ -1797,8 +1866,20 @@ __device__ __forceinline__ void ppo_pass0_wave(const Params &p, const PpoStepArg
         }
 #pragma unroll
         for (int it = 0; it < 32 * NPC / WAVE; it++) *(vf4 *)(tile + slot[it]) = v[it];
+        if constexpr (OPP) {  // the other agent's rows: one sim row and one tile row on from the trainee's
+            const int d = 1 - 2 * trainee;
+#pragma unroll
+            for (int it = 0; it < 32 * NPC / WAVE; it++) {
+                const int f = it * WAVE + lane, m = f / NPC, t = f - m * NPC;
+                const int i = 32 * (t >> 2) + 16 * P + 4 * (t & 3);
+                v[it] = w0 + m < W ? *(const vf4 *)(src + ((int64_t)m * N + d) * OW + i) : vf4{0.f, 0.f, 0.f, 0.f};
+            }
+#pragma unroll
+            for (int it = 0; it < 32 * NPC / WAVE; it++) *(vf4 *)(tile + slot[it] + d * PPS_RS) = v[it];
+        }
         wave_sync();
         ppo_layer1_pass<P>(tile, S.wt, acc, trainee, pl, pq);
+        if constexpr (OPP) ppo_layer1_pass<P>(tile, S.ow, oacc, 1 - trainee, pl, pq);
         wave_sync();
     };
     pass(std::integral_constant<int, 0>());
@@ -1831,6 +1912,7 @@ __device__ __forceinline__ void ppo_pass0_wave(const Params &p, const PpoStepArg
     BucketLds<32> &bl = *(BucketLds<32> *)(tile + 32 * 33);
     if (a.stochastic) bucket_pass_spread<32, true, 1>(pa, lt, w0, lane, bl, nullptr, &noise);
     else bucket_pass_spread<32, true, 0>(pa, lt, w0, lane, bl, nullptr, &noise);
+    if constexpr (OPP) ppo_opponent_tail(p, S.ow, tile, oacc, onoise, trainee, a.seed ^ PPO_OPP_KEY, a.step0, w0, lane);
     wave_sync();  // the tile is rewritten by step 0
 }
 
@@ -1853,17 +1935,27 @@ __global__ __launch_bounds__(WAVE * WPG, 2) void k_step_ppo(const Params p, cons
 // another's systems.  A wave reads only what its own lanes wrote (same wave,
 // same vector L1: coherent; the fence orders the store and the loads).  Each
 // step computes exactly what k_step_ppo computes (bit-identical).
-template <int WPG>
-__global__ __launch_bounds__(WAVE * WPG, 2) void k_rollout_ppo(const Params p, const PpoStepArgs a0, int32_t steps)
+//
+// OPP, self-play (bb_rollout_policy with a frozen opponent above the fused
+// rollout's bound): the opponent's image beside the trainee's, filled before
+// the same one barrier; its network runs in the step-0 pass and after every
+// step but the last (ppo_step_wave), still wave-local: each step then is
+// bit-identical to a k_policy launch per agent and a k_step launch.  Two
+// images and 15 KB of tile per wave leave room for 4 waves (124 KB: one
+// workgroup per CU, so a wave per SIMD and its whole register file, MINW 1)
+// or 6 (154 KB, two waves on half the SIMDs: the 256-register budget).
+template <int WPG, bool OPP = false, int MINW = 2>
+__global__ __launch_bounds__(WAVE * WPG, MINW) void k_rollout_ppo(const Params p, const PpoStepArgs a0, int32_t steps)
 {
     if constexpr (BB_N == 2) {
-        __shared__ PpoStepLds<WPG> S;
+        __shared__ PpoStepLds<WPG, OPP> S;
         const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x / WAVE);
         const int lane = (int)threadIdx.x % WAVE;
         policy_weights_to_lds(S.wt, a0.w, (int)threadIdx.x, WPG * WAVE);
+        if constexpr (OPP) policy_weights_to_lds(S.ow, a0.opp, (int)threadIdx.x, WPG * WAVE);
         lds_barrier();
         if (a0.pass0) {
-            ppo_pass0_wave<WPG>(p, a0, S, (int)blockIdx.x, wave, lane);
+            ppo_pass0_wave<WPG, OPP>(p, a0, S, (int)blockIdx.x, wave, lane);
             // step 0 reads the action column the pass wrote
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         }
@@ -1876,8 +1968,8 @@ __global__ __launch_bounds__(WAVE * WPG, 2) void k_rollout_ppo(const Params p, c
             __asm__ volatile("" : "+s"(k_t), "+s"(blk_t), "+s"(wave_t));
             __asm__ volatile("" : "+v"(lane_t));
             const PpoStepArgs a = ppo_loop_args(a0, k_t, steps, W);
-            if (k_t + 1 < steps) ppo_step_wave<WPG, false, true>(p, a, S, blk_t, wave_t, lane_t);
-            else ppo_step_wave<WPG, true, true>(p, a, S, blk_t, wave_t, lane_t);
+            if (k_t + 1 < steps) ppo_step_wave<WPG, false, true, OPP>(p, a, S, blk_t, wave_t, lane_t);
+            else ppo_step_wave<WPG, true, true, OPP>(p, a, S, blk_t, wave_t, lane_t);
             // this step's state / action stores before the next step's loads
             __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
         }
@@ -2986,6 +3078,14 @@ hipError_t launch_rollout_ppo_2(const Params &p, const PpoStepArgs &a, int32_t s
     const int wpg = waves >= 8 * cus ? 8 : waves >= 4 * cus ? 4 : waves >= 2 * cus ? 2 : 1;
     const dim3 grid((unsigned)((waves + wpg - 1) / wpg)), block(WAVE * wpg);
     if (steps < 1) return hipSuccess;
+    if (a.has_opp) {
+        // self-play: one workgroup size at every world count (LDS-bound, above)
+        constexpr int OWPG = PPO_SELFPLAY_WPG;
+        const dim3 ogrid((unsigned)((waves + OWPG - 1) / OWPG));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_ppo<OWPG, true, OWPG == 4 ? 1 : 2>), ogrid, dim3(WAVE * OWPG), 0,
+                           s, p, a, steps);
+        return hipGetLastError();
+    }
     switch (wpg) {
     case 8: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_ppo<8>), grid, block, 0, s, p, a, steps); break;
     case 4: hipLaunchKernelGGL(HIP_KERNEL_NAME(k_rollout_ppo<4>), grid, block, 0, s, p, a, steps); break;

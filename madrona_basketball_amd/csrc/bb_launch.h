@@ -89,12 +89,28 @@ struct PpoStepArgs {
     float *obs0;
     int32_t *act0;
     float *log_prob0, *value0;
+    // k_rollout_ppo's self-play form (has_opp; 0: none): the frozen opponent's
+    // policy acts for the other agent in the launch's step-0 pass and after
+    // every step but the last (sampling, key seed ^ 0x9E3779B9, from the other
+    // agent's rows in the wave's tile; nothing of it is recorded)
+    PolicyWeights opp;
+    int32_t has_opp;
 };
+// Waves per workgroup of k_rollout_ppo's self-play form (two weight images,
+// 65 KB of LDS, beside 15 KB of tile per wave): 4 (124 KB, one workgroup per
+// CU, a wave per SIMD with its whole register file) or 6 (154 KB, 256
+// registers) -- DESIGN.md 5.5 "fused self-play step" has the A/B.
+#ifndef BB_PPO_SELFPLAY_WPG
+#define BB_PPO_SELFPLAY_WPG 4
+#endif
+constexpr int PPO_SELFPLAY_WPG = BB_PPO_SELFPLAY_WPG;
+static_assert(PPO_SELFPLAY_WPG == 4 || PPO_SELFPLAY_WPG == 6, "k_rollout_ppo's self-play workgroup");
 // N = 2 only (hipErrorNotSupported otherwise)
 hipError_t launch_step_ppo(int n, const Params &p, const PpoStepArgs &a, hipStream_t s);
 // The `steps` steps of a rollout in one launch (k_rollout_ppo<2>): `a` holds
 // step 0's arguments (outputs of step k at k x W past them; its `last` is
-// ignored), value_last the next_value output.  N = 2 only.
+// ignored), value_last the next_value output; with a.has_opp the self-play
+// form.  N = 2 only.
 hipError_t launch_rollout_ppo(int n, const Params &p, const PpoStepArgs &a, int32_t steps, hipStream_t s);
 
 // Trajectory recorder (bb_record): NSEG column segments per recorded world.
@@ -122,7 +138,8 @@ enum DiagKey : int {
     DIAG_POLICY_WG = 8,                  // k_policy_wg: 0 never, 1 always (else from 98 304 rows)
     DIAG_PPO_OPP_WAVES = 9,              // k_rollout_selfplay's opponent waves: 1 or 2 (2 only at one workgroup per CU)
     DIAG_PPO_STEP_TICKET = 10,           // 1: bb_policy_ppo_step finishes in k_ppo_step's last workgroup (ticket) instead of k_adam_step
-    DIAG_KEYS = 11
+    DIAG_PPO_SELFPLAY_STEP_MIN_WORLDS = 11,  // with an opponent: the fused PPO step (k_rollout_ppo's self-play form) from this many worlds (0 never)
+    DIAG_KEYS = 12
 };
 extern int diag_override[DIAG_KEYS];
 inline int diag_or(int key, int dflt)

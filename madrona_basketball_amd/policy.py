@@ -458,9 +458,9 @@ class FusedPolicy:
         `opponent` acts for the other agent, env.py:127-143]; step) with the
         buffer stores of ppo.py:129-134 and next_value = evaluate(last obs).
         Bit for bit n x (act(); [opponent.act()]; sim.step()) with the same reads.
-        Any entry of `buffers` may be None (not recorded).  On gfx950 (2 agents,
-        up to 16 384 worlds) one fused launch runs every step, with the
-        opponent's network in it when there is one (nothing of the opponent is
+        Any entry of `buffers` may be None (not recorded).  On gfx950 (2 agents)
+        one fused launch runs every step, with the opponent's network in it
+        when there is one, at every world count (nothing of the opponent is
         recorded); per_step=True forces a policy launch per acting agent + a
         step launch per step.  Returns
         the elapsed device ms when time_kernels."""
