@@ -24,6 +24,8 @@
  *   bb_policy_forward   <- Agent.forward of scripts/agent.py:140-154 (32 channels,
  *                          2 layers, env.py:107) + the action write of
  *                          scripts/env.py:147, fused on the device
+ *   bb_policy_forward_wide <- the same for Agent(envs.get_input_dim(), ...) at the
+ *                          184 / 264 / 344 / 424-float rows of 4 to 10 agents
  *   bb_rollout_policy   <- rollout() of scripts/ppo.py:61-141: n x (agent(obs);
  *                          env.step; buffer stores) + agent.evaluate(obs_)
  *   bb_set_action       <- Manager::setAction          src/mgr.cpp:270-293
@@ -244,6 +246,21 @@ typedef struct bb_policy_weights {
 int bb_policy_forward(const bb_policy_weights *w, int32_t exec_mode, int32_t gpu_id, const float *obs,
                       int64_t rows, int64_t obs_stride, int32_t *actions, int64_t action_stride, float *log_prob,
                       float *value, int32_t stochastic, uint32_t seed, uint32_t step, void *stream);
+
+/* bb_policy_forward at the observation widths of the 2v2 to 5v5 games: the
+ * network Agent(envs.get_input_dim(), num_channels = 32, num_layers = 2)
+ * builds (scripts/agent.py:108-124) when the simulator exports in_dim =
+ * bb_obs_width(N) = 184, 264, 344 or 424 floats (N = 4, 6, 8, 10).  w as above
+ * with obs_mean, obs_inv [in_dim] and w1 [32][in_dim].  Rows, outputs and
+ * sampling as bb_policy_forward (reads in_dim floats at obs + r * obs_stride,
+ * nothing behind them); actions may be NULL (log_prob / value only,
+ * agent.evaluate, agent.py:168-170).  BB_ERR_INVALID_ARG for any other
+ * in_dim, obs_stride < in_dim, a NULL weight or rows / w1 / w2 / head_w not
+ * 16-byte aligned. */
+int bb_policy_forward_wide(const bb_policy_weights *w, int32_t in_dim, int32_t exec_mode, int32_t gpu_id,
+                           const float *obs, int64_t rows, int64_t obs_stride, int32_t *actions, int64_t act_stride,
+                           float *log_prob, float *value, int32_t stochastic, uint32_t seed, uint32_t step,
+                           void *stream);
 
 /* PPO's rollout on the device (scripts/ppo.py:61-141 over scripts/env.py:126-170;
  * the reference's 2-agent game).  For k = 0..n-1:

@@ -42,7 +42,7 @@ ABI_SYMBOLS = [
     "bb_default_config", "bb_obs_width", "bb_buffer_bytes", "bb_create",
     "bb_create_with_buffers", "bb_destroy", "bb_step", "bb_step_n",
     "bb_write_random_actions", "bb_step_n_staged", "bb_fill_random_actions", "bb_rollout",
-    "bb_record_words", "bb_record", "bb_policy_forward", "bb_rollout_policy",
+    "bb_record_words", "bb_record", "bb_policy_forward", "bb_policy_forward_wide", "bb_rollout_policy",
     "bb_policy_ppo_grad", "bb_policy_ppo_grad_workspace_bytes",
     "bb_policy_advantages", "bb_policy_advantages_workspace_bytes",
     "bb_policy_adam_step", "bb_policy_ppo_step", "bb_policy_ppo_step_workspace_bytes",
@@ -152,6 +152,8 @@ def load():
         "bb_record_words": (i32, [i32]),
         "bb_policy_forward": (ctypes.c_int, [ctypes.POINTER(PolicyWeights), i32, i32, vp, i64, i64, vp, i64, vp, vp,
                                              i32, u32, u32, vp]),
+        "bb_policy_forward_wide": (ctypes.c_int, [ctypes.POINTER(PolicyWeights), i32, i32, i32, vp, i64, i64, vp, i64,
+                                                  vp, vp, i32, u32, u32, vp]),
         "bb_record": (ctypes.c_int, [vp, i64, i32, vp, i64, vp]),
         "bb_rollout_policy": (ctypes.c_int, [vp, ctypes.POINTER(PolicyWeights), ctypes.POINTER(PolicyWeights), i32,
                                              i32, i32, u32, u32, ctypes.POINTER(PolicyRolloutBuffers), u32, vp,

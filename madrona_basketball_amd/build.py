@@ -36,11 +36,12 @@ NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
 UNITS = ([("bb_kernels.hip", [f"-DBB_N={n}", *KERNEL_FLAGS, *N_FLAGS.get(n, [])], f"bb_kernels_n{n}.o")
           for n in AGENT_COUNTS]
          + [("bb_common.hip", [], "bb_common.o"), ("bb_host.hip", [], "bb_host.o"),
-            ("bb_policy.hip", [], "bb_policy.o"), ("bb_policy_grad.hip", NO_PK_F32, "bb_policy_grad.o"),
+            ("bb_policy.hip", [], "bb_policy.o"), ("bb_policy_wide.hip", [], "bb_policy_wide.o"),
+            ("bb_policy_grad.hip", NO_PK_F32, "bb_policy_grad.o"),
             ("bb_advantages.hip", NO_PK_F32, "bb_advantages.o"),
             ("bb_policy_step.hip", NO_PK_F32, "bb_policy_step.o")])
 SOURCES = sorted({u[0] for u in UNITS})
-HEADERS = ["bb_math.h", "bb_rng.h", "bb_sim.h", "bb_launch.h", "bb_policy.h", "bb_policy_dev.h",
+HEADERS = ["bb_math.h", "bb_rng.h", "bb_sim.h", "bb_launch.h", "bb_policy.h", "bb_policy_dev.h", "bb_policy_wide.h",
            "bb_policy_grad.h", "bb_advantages.h", "bb_policy_step.h"]
 ARCH = os.environ.get("BB_OFFLOAD_ARCH", "gfx950")
 

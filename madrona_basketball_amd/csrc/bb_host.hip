@@ -26,6 +26,7 @@
 #include "bb_launch.h"
 #include "bb_policy_grad.h"
 #include "bb_policy_step.h"
+#include "bb_policy_wide.h"
 #include "bb_sim.h"
 
 namespace {
@@ -953,6 +954,39 @@ int bb_policy_forward(const bb_policy_weights *w, int32_t exec_mode, int32_t gpu
     DeviceGuard g(gpu_id);
     hipError_t e = bb::launch_policy(a, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "launch policy kernel");
+    return BB_OK;
+}
+
+int bb_policy_forward_wide(const bb_policy_weights *w, int32_t in_dim, int32_t exec_mode, int32_t gpu_id,
+                           const float *obs, int64_t rows, int64_t obs_stride, int32_t *actions, int64_t act_stride,
+                           float *log_prob, float *value, int32_t stochastic, uint32_t seed, uint32_t step, void *stream)
+{
+    if (!bb::pol_wide_width(in_dim))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_forward_wide: in_dim must be 184, 264, 344 or 424");
+    if (!w || !obs || rows < 0 || obs_stride < in_dim || (actions && act_stride < 6))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_forward_wide: arguments");
+    const float *req[] = {w->obs_mean, w->obs_inv, w->w1, w->b1, w->ln1_w, w->ln1_b, w->w2, w->b2, w->ln2_w,
+                          w->ln2_b, w->head_w, w->head_b};
+    for (const float *ptr : req)
+        if (!ptr) return fail(BB_ERR_INVALID_ARG, "bb_policy_forward_wide: a weight pointer is NULL");
+    if ((((uintptr_t)obs) & 15u) || (obs_stride & 3) || (((uintptr_t)w->w1) & 15u) || (((uintptr_t)w->w2) & 15u) ||
+        (((uintptr_t)w->head_w) & 15u))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_forward_wide: obs rows, w1, w2 and head_w must be 16-byte aligned");
+    bb::PolicyArgs a{};
+    a.w = bb::PolicyWeights{w->obs_mean, w->obs_inv, w->w1, w->b1, w->ln1_w, w->ln1_b,
+                            w->w2, w->b2, w->ln2_w, w->ln2_b, w->head_w, w->head_b};
+    a.obs = obs; a.obs_stride = obs_stride; a.rows = rows;
+    a.actions = actions; a.act_stride = act_stride;
+    a.log_prob = log_prob; a.value = value;
+    a.stochastic = stochastic ? 1 : 0; a.seed = seed; a.step = step;
+    if (exec_mode == BB_EXEC_CPU) {
+        bb::host_policy_wide(a, in_dim);
+        return BB_OK;
+    }
+    if (exec_mode != BB_EXEC_CUDA) return fail(BB_ERR_INVALID_ARG, "bb_policy_forward_wide: exec_mode");
+    DeviceGuard g(gpu_id);
+    hipError_t e = bb::launch_policy_wide(a, in_dim, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "launch wide policy kernel");
     return BB_OK;
 }
 

@@ -211,6 +211,9 @@ hipError_t launch_random_actions(int n, const Params &p, uint32_t seed, uint32_t
 hipError_t launch_poke(int32_t *dst, int count, const int32_t *vals, hipStream_t s);
 hipError_t launch_policy(const PolicyArgs &a, hipStream_t s);
 void host_policy(const PolicyArgs &a);
+// The policy at observation widths 184, 264, 344, 424 (bb_policy_wide.h / bb_policy_wide.hip)
+hipError_t launch_policy_wide(const PolicyArgs &a, int in_dim, hipStream_t s);
+void host_policy_wide(const PolicyArgs &a, int in_dim);
 // PPO's minibatch loss and gradient (bb_policy_grad.h / bb_policy_grad.hip)
 struct PpoGradArgs;
 hipError_t launch_ppo_grad(const PpoGradArgs &a, hipStream_t s);

@@ -251,20 +251,12 @@ BB_HD void pol_layernorm_relu(float *h, const float *w, const float *b)
     for (int c = 0; c < 32; c++) h[c] = pol_relu(((d[c] * inv) * w[c]) + b[c]);
 }
 
-// One row on the host, in the kernel's arithmetic order.
-inline void policy_row_host(const PolicyArgs &a, int64_t r)
+// A row's layers after layer 1 on the host (h1: W1 x + b1), in the kernel's
+// arithmetic order: LayerNorm, layer 2, heads, bucket pass and the outputs.
+inline void policy_row_host_rest(const PolicyArgs &a, int64_t r, float *h1)
 {
     const PolicyWeights &W = a.w;
-    const float *o = a.obs + r * a.obs_stride;
-    float x[POL_IN];
-    for (int k = 0; k < POL_IN; k++) x[k] = pol_clamp((o[k] - W.obs_mean[k]) * W.obs_inv[k]);
-    float h1[POL_HID], h2[POL_HID], out[POL_HEAD];
-    for (int n = 0; n < POL_HID; n++) {
-        float acc = 0.f;
-        for (int j = 0; j < 32; j++)
-            for (int q = 0; q < 4; q++) acc = __builtin_fmaf(x[32 * q + j], W.w1[n * POL_IN + 32 * q + j], acc);
-        h1[n] = acc + W.b1[n];
-    }
+    float h2[POL_HID], out[POL_HEAD];
     pol_layernorm_relu(h1, W.ln1_w, W.ln1_b);
     for (int n = 0; n < POL_HID; n++) {
         float acc = 0.f;
@@ -282,8 +274,6 @@ inline void policy_row_host(const PolicyArgs &a, int64_t r)
     int32_t act[6];
     float lp;
     pol_select(out, a.stochastic != 0, a.seed, a.step, (uint32_t)r + a.key_row0, act, &lp);
-    if (a.obs_out)
-        for (int k = 0; k < POL_IN; k++) a.obs_out[r * POL_IN + k] = o[k];
     if (a.actions) {
         int32_t *d = a.actions + r * a.act_stride;
         for (int b = 0; b < 6; b++) d[b] = act[b];
@@ -296,6 +286,25 @@ inline void policy_row_host(const PolicyArgs &a, int64_t r)
         a.rew_out[r] = a.rew_src[r * a.rd_stride];
         a.done_out[r] = a.done_src[r * a.rd_stride];
     }
+}
+
+// One row on the host, in the kernel's arithmetic order.
+inline void policy_row_host(const PolicyArgs &a, int64_t r)
+{
+    const PolicyWeights &W = a.w;
+    const float *o = a.obs + r * a.obs_stride;
+    float x[POL_IN];
+    for (int k = 0; k < POL_IN; k++) x[k] = pol_clamp((o[k] - W.obs_mean[k]) * W.obs_inv[k]);
+    float h1[POL_HID];
+    for (int n = 0; n < POL_HID; n++) {
+        float acc = 0.f;
+        for (int j = 0; j < 32; j++)
+            for (int q = 0; q < 4; q++) acc = __builtin_fmaf(x[32 * q + j], W.w1[n * POL_IN + 32 * q + j], acc);
+        h1[n] = acc + W.b1[n];
+    }
+    if (a.obs_out)
+        for (int k = 0; k < POL_IN; k++) a.obs_out[r * POL_IN + k] = o[k];
+    policy_row_host_rest(a, r, h1);
 }
 
 }  // namespace bb

@@ -499,8 +499,10 @@ __device__ __forceinline__ void policy_weights_to_lds(PolicyLdsWeights &L, const
 // Layer 2 + LayerNorm + ReLU, then the heads, of one 16-row M-tile whose
 // layer-1 output is in tm[16][33], with the weights in LDS: row r's 19 logits
 // and value into tm[r][0..19].  The same operands in the same order as
-// policy_layers' second loop (lane (c, q): k = 8q + j).
-__device__ __forceinline__ void policy_tail_lds(const PolicyLdsWeights &L, float (*tm)[33], int c, int q)
+// policy_layers' second loop (lane (c, q): k = 8q + j).  LW: any LDS image
+// with PolicyLdsWeights' w2, wh and cst members (bb_policy_wide.hip has its own).
+template <class LW>
+__device__ __forceinline__ void policy_tail_lds(const LW &L, float (*tm)[33], int c, int q)
 {
 #pragma unroll
     for (int layer = 0; layer < 2; layer++) {

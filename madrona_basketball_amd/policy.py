@@ -1,9 +1,11 @@
 """Fused policy inference: the reference's Agent
 (scripts/agent.py:108-154, 32 channels, 2 layers, buckets [2,8,3,2,2,2]) run
-by one gfx950 kernel (bb_policy_forward, csrc/bb_policy.hip) that writes its
-actions straight into the simulator's action tensor -- the
-`actions, log_probs, values = agent(obs)` + `actions[:, i] = a` pair of
-scripts/ppo.py:67 / scripts/env.py:147 without a round trip through torch.
+by one gfx950 kernel (bb_policy_forward, csrc/bb_policy.hip; at the 184 / 264 /
+344 / 424-float rows of 4, 6, 8 and 10 agents bb_policy_forward_wide,
+csrc/bb_policy_wide.hip) that writes its actions straight into the simulator's
+action tensor -- the `actions, log_probs, values = agent(obs)` +
+`actions[:, i] = a` pair of scripts/ppo.py:67 / scripts/env.py:147 without a
+round trip through torch.  The rollout and the PPO update are 128-wide only.
 
 FusedPolicy.from_agent(agent) snapshots the weights of any torch module with
 the reference Agent's layout (obs_norm.mean/var, backbone Linear/LayerNorm,
@@ -23,6 +25,7 @@ from .madrona import ExecMode
 
 BUCKETS = (2, 8, 3, 2, 2, 2)
 IN, HID, LOGITS, HEAD = 128, 32, 19, 32
+WIDTHS = (128, 184, 264, 344, 424)  # bb_obs_width(N), N = 2, 4, 6, 8, 10: the first layer's input widths served
 PARAMS = HID * IN + HID * HID + 6 * HID + (LOGITS + 1) * (HID + 1)  # 5 972
 
 
@@ -47,19 +50,20 @@ class RunningStats:
         self.count = torch.ones((), dtype=torch.float64, device=device)
 
 
-def make_agent(seed: int = 0) -> torch.nn.Module:
+def make_agent(seed: int = 0, input_dim: int = IN) -> torch.nn.Module:
     """A torch module with the reference Agent's layout and initialisation
     (scripts/agent.py:97-131: Kaiming-normal backbone, orthogonal heads at gain
     0.01, zero biases, identity observation normaliser) -- random weights of
-    that architecture for benchmarks and tests (no checkpoints here)."""
+    that architecture for benchmarks and tests (no checkpoints here).  input_dim:
+    the observation width, envs.get_input_dim() (128 for the 2-agent game)."""
     g = torch.Generator().manual_seed(seed)
     m = torch.nn.Module()
     m.action_buckets = list(BUCKETS)
-    m.backbone = torch.nn.Sequential(torch.nn.Linear(IN, HID), torch.nn.LayerNorm(HID), torch.nn.ReLU(),
+    m.backbone = torch.nn.Sequential(torch.nn.Linear(input_dim, HID), torch.nn.LayerNorm(HID), torch.nn.ReLU(),
                                      torch.nn.Linear(HID, HID), torch.nn.LayerNorm(HID), torch.nn.ReLU())
     m.actor = torch.nn.Linear(HID, LOGITS)
     m.critic = torch.nn.Linear(HID, 1)
-    m.obs_norm = _ObsNorm(IN)
+    m.obs_norm = _ObsNorm(input_dim)
     with torch.no_grad():
         for lin in (m.backbone[0], m.backbone[3]):
             torch.nn.init.kaiming_normal_(lin.weight, torch.nn.init.calculate_gain("relu"), generator=g)
@@ -77,7 +81,9 @@ def agent_from_state_dict(state_dict: dict, device=None) -> torch.nn.Module:
     value_norm / count buffers are not used by inference).  Load checkpoints
     with torch.load(path, weights_only=True), as Agent.load does
     (scripts/agent.py:180-182)."""
-    m = make_agent(0)
+    if "backbone.0.weight" not in state_dict:
+        raise KeyError("state_dict lacks ['backbone.0.weight']")
+    m = make_agent(0, int(torch.as_tensor(state_dict["backbone.0.weight"]).shape[-1]))  # the width it was trained at
     own = m.state_dict()
     missing = [k for k in own if k not in state_dict]
     if missing:
@@ -124,10 +130,13 @@ class FusedPolicy:
         a = self.agent
         lin = [m for m in a.backbone if isinstance(m, torch.nn.Linear)]
         lns = [m for m in a.backbone if isinstance(m, torch.nn.LayerNorm)]
-        if (len(lin) != 2 or lin[0].in_features != IN or lin[0].out_features != HID or lin[1].out_features != HID
-                or a.actor.out_features != LOGITS or tuple(a.action_buckets) != BUCKETS):
-            raise ValueError("FusedPolicy supports the reference configuration: input 128, num_channels 32, "
-                             "num_layers 2, buckets [2, 8, 3, 2, 2, 2] (scripts/env.py:107)")
+        if (len(lin) != 2 or lin[0].in_features not in WIDTHS or lin[0].out_features != HID
+                or lin[1].out_features != HID or a.actor.out_features != LOGITS
+                or tuple(a.action_buckets) != BUCKETS or tuple(a.obs_norm.mean.shape) != (lin[0].in_features,)):
+            raise ValueError("FusedPolicy supports the reference configuration: input 128 (or the 184, 264, 344, 424 "
+                             "of 4 to 10 agents), num_channels 32, num_layers 2, buckets [2, 8, 3, 2, 2, 2] "
+                             "(scripts/env.py:107)")
+        self.in_dim = lin[0].in_features
         dev, f32 = self.device, torch.float32
 
         def t(x):
@@ -153,6 +162,7 @@ class FusedPolicy:
         """A copy of the packed weights on another device (same bits)."""
         p = FusedPolicy(device)
         p.agent = getattr(self, "agent", None)
+        p.in_dim = self.in_dim
         p._tensors = {k: v.to(p.device).contiguous() for k, v in self._tensors.items()}
         p._w = _lib.PolicyWeights(**{k: v.data_ptr() for k, v in p._tensors.items()})
         return p
@@ -164,11 +174,15 @@ class FusedPolicy:
 
     def forward_into(self, obs: torch.Tensor, actions: torch.Tensor, log_prob: torch.Tensor = None,
                      value: torch.Tensor = None, stochastic: bool = True, seed: int = 0, step: int = 0) -> None:
-        """obs [R, >=128] float32 rows (any row stride, e.g. obs_tensor[:, agent]);
-        actions [R, 6] int32 rows (any row stride, e.g. action_tensor[:, agent])."""
-        rows = obs.shape[0]
-        if obs.dim() != 2 or obs.shape[1] < IN or obs.stride(1) != 1 or obs.dtype != torch.float32:
-            raise ValueError("obs must be float32 [rows, >=128] with unit column stride")
+        """obs [R, >= in_dim] float32 rows (any row stride, e.g. obs_tensor[:, agent])
+        of the simulator the agent was built for: the first in_dim floats of a row
+        are the network's input, so in_dim must be that simulator's observation
+        width, bb_obs_width(N) (128, 184, 264, 344, 424 for 2 to 10 agents; act_all
+        checks it); actions [R, 6] int32 rows (any row stride, e.g.
+        action_tensor[:, agent])."""
+        rows, in_dim = obs.shape[0], self.in_dim
+        if obs.dim() != 2 or obs.shape[1] < in_dim or obs.stride(1) != 1 or obs.dtype != torch.float32:
+            raise ValueError(f"obs must be float32 [rows, >={in_dim}] with unit column stride")
         if (actions.dim() != 2 or actions.shape != (rows, 6) or actions.stride(1) != 1
                 or actions.dtype != torch.int32):
             raise ValueError("actions must be int32 [rows, 6] with unit column stride")
@@ -179,8 +193,12 @@ class FusedPolicy:
             if t is not None and (t.shape != (rows,) or not t.is_contiguous() or t.dtype != torch.float32):
                 raise ValueError("log_prob / value must be contiguous float32 [rows]")
         mode = ExecMode.CUDA if self.device.type == "cuda" else ExecMode.CPU
-        _lib.check(_lib.load().bb_policy_forward(
-            ctypes.byref(self._w), int(mode), self.device.index if self.device.index is not None else -1,
+        lib = _lib.load()
+        # 128: bb_policy_forward, as ever; the wider rows: bb_policy_forward_wide
+        entry = lib.bb_policy_forward if in_dim == IN else lib.bb_policy_forward_wide
+        width = () if in_dim == IN else (in_dim,)
+        _lib.check(entry(
+            ctypes.byref(self._w), *width, int(mode), self.device.index if self.device.index is not None else -1,
             ctypes.c_void_p(obs.data_ptr()), rows, obs.stride(0), ctypes.c_void_p(actions.data_ptr()),
             actions.stride(0), ctypes.c_void_p(None if log_prob is None else log_prob.data_ptr()),
             ctypes.c_void_p(None if value is None else value.data_ptr()), 1 if stochastic else 0,
@@ -203,6 +221,24 @@ class FusedPolicy:
         act = sim.action_tensor().to_torch()[:, agent_idx]
         self.forward_into(obs, act, log_prob, value, stochastic, seed, step)
 
+    def act_all(self, sim, log_prob: torch.Tensor = None, value: torch.Tensor = None, stochastic: bool = True,
+                seed: int = 0, step: int = 0) -> None:
+        """One shared policy for every agent of every world, in one launch: the
+        [W * N, obs_width] view of the observation tensor into the [W * N, 6] view
+        of the action tensor (row w * N + i: agent i of world w; log_prob / value
+        [W * N]).  The policy's in_dim must be the simulator's observation width."""
+        obs = sim.observations_tensor().to_torch()
+        if obs.shape[-1] != self.in_dim:
+            raise ValueError(f"a {self.in_dim}-input policy cannot act for a simulator of {obs.shape[1]} agents "
+                             f"(observation width {obs.shape[-1]})")
+        act = sim.action_tensor().to_torch()
+        self.forward_into(obs.view(-1, obs.shape[-1]), act.view(-1, 6), log_prob, value, stochastic, seed, step)
+
+    def _require_128(self, what: str) -> None:
+        if self.in_dim != IN:
+            raise ValueError(f"{what} is built for the 128-wide configuration (the 2-agent game); this policy has "
+                             f"{self.in_dim} inputs: inference only (forward_into, act, act_all)")
+
     # ------------------------------------------------------------- PPO update
     def ppo_grad(self, obs: torch.Tensor, actions: torch.Tensor, log_prob: torch.Tensor, value: torch.Tensor,
                  advantages: torch.Tensor, returns: torch.Tensor, idx: torch.Tensor = None, clip_coef: float = 0.2,
@@ -219,6 +255,7 @@ class FusedPolicy:
         tensor on the device: loss, pg_loss, c_loss before vf_coef, mean entropy
         (no host synchronisation).  head_grad keeps the packed head's gradient
         ([32, 32] and [32]: rows 0-18 the actor, 19 the critic, 20-31 zero)."""
+        self._require_128("ppo_grad")
         batch, m = self._ppo_args(obs, actions, log_prob, value, advantages, returns, idx)
         direct = self._params(True)[:8]
         dev, f32, a = self.device, torch.float32, self.agent
@@ -311,6 +348,7 @@ class FusedPolicy:
         (the observation statistics are not: refresh() after compute_advantages
         as before).  Returns float32 [2] on the device: the gradient norm before
         clipping and the clip factor (no host synchronisation)."""
+        self._require_128("optimizer_step")
         params, grads, st, hyper = self._step_args(state, lr, max_grad_norm, betas, eps, False)
         dev = self.device
         out2 = torch.empty((2,), dtype=torch.float32, device=dev)
@@ -331,6 +369,7 @@ class FusedPolicy:
         ppo_grad() followed by optimizer_step().  Returns float32 [6] on the
         device: loss, pg_loss, c_loss, entropy, gradient norm before clipping,
         clip factor."""
+        self._require_128("ppo_minibatch")
         batch, m = self._ppo_args(obs, actions, log_prob, value, advantages, returns, idx)
         params, grads, st, hyper = self._step_args(state, lr, max_grad_norm, betas, eps, True)
         dev, lib = self.device, _lib.load()
@@ -356,6 +395,7 @@ class FusedPolicy:
         R // num_minibatches rows at range(0, R, minibatch_size) -- a short last
         one when R is not divisible, as ppo.py:188 has it -- each one
         ppo_minibatch(**kw).  Returns float32 [steps, 6], one row per minibatch."""
+        self._require_128("ppo_update")
         rows = obs.shape[0]
         mb = rows // int(num_minibatches)
         if mb < 1:
@@ -393,6 +433,7 @@ class FusedPolicy:
         tensor on the device: mean and unbiased std of A before normalisation,
         value_norm's new mean and var (no host synchronisation; torch's current
         stream)."""
+        self._require_128("compute_advantages")
         dev, f32, f64 = self.device, torch.float32, torch.float64
         obs = buffers.get("obs")
         if (obs is None or obs.dim() != 3 or obs.shape[2] != IN or obs.dtype != f32 or not obs.is_contiguous()
@@ -464,6 +505,7 @@ class FusedPolicy:
         recorded); per_step=True forces a policy launch per acting agent + a
         step launch per step.  Returns
         the elapsed device ms when time_kernels."""
+        self._require_128("rollout")
         W = sim.num_worlds
         shapes = {"obs": ((n, W, IN), torch.float32), "actions": ((n, W, 6), torch.int32),
                   "log_prob": ((n, W), torch.float32), "value": ((n, W), torch.float32),
