@@ -349,6 +349,24 @@ int bb_policy_ppo_grad(const bb_policy_weights *w, int32_t exec_mode, int32_t gp
                        int64_t workspace_bytes, void *stream);
 int64_t bb_policy_ppo_grad_workspace_bytes(int64_t m);
 
+/* bb_policy_ppo_grad for the networks bb_policy_forward_wide serves: in_dim =
+ * 184, 264, 344 or 424 inputs.  batch->obs is float [rows][in_dim] contiguous
+ * (16-byte aligned; every width is a multiple of 8, so every row is), w->w1,
+ * w->obs_mean / obs_inv and grads->w1 are [32][in_dim] / [in_dim]; everything
+ * else as bb_policy_ppo_grad: the same loss, the same gathered rows, loss4, no
+ * atomics, no synchronisation.  On gfx950 two passes over the minibatch rows
+ * and a reduce: the first runs forward, loss and backward and leaves dloss/dz1
+ * [m][32] in the workspace, the second multiplies it into dW1 against the
+ * re-read rows.  workspace: bb_policy_ppo_grad_wide_workspace_bytes(in_dim, m)
+ * bytes on the device, 16-byte aligned (CUDA mode; unused in CPU mode): the dz1
+ * rows and both passes' partial sums; 0 for another in_dim or m <= 0.
+ * BB_ERR_INVALID_ARG (nothing launched) for any other in_dim and for whatever
+ * bb_policy_ppo_grad refuses. */
+int64_t bb_policy_ppo_grad_wide_workspace_bytes(int32_t in_dim, int64_t m);
+int bb_policy_ppo_grad_wide(const bb_policy_weights *w, int32_t in_dim, int32_t exec_mode, int32_t gpu_id,
+                            const bb_ppo_batch *batch, const bb_ppo_coef *coef, const bb_policy_grads *grads,
+                            float *loss4, void *workspace, int64_t workspace_bytes, void *stream);
+
 /* PPO's phase between the rollout and the minibatch updates (scripts/ppo.py:144-177
  * compute_advantages over scripts/agent.py:28-50 RunningMeanStd), on the
  * buffers bb_rollout_policy filled: obs float [steps][worlds][128] (16-byte

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "bb_write_random_actions", "bb_step_n_staged", "bb_fill_random_actions", "bb_rollout",
     "bb_record_words", "bb_record", "bb_policy_forward", "bb_policy_forward_wide", "bb_rollout_policy",
     "bb_policy_ppo_grad", "bb_policy_ppo_grad_workspace_bytes",
+    "bb_policy_ppo_grad_wide", "bb_policy_ppo_grad_wide_workspace_bytes",
     "bb_policy_advantages", "bb_policy_advantages_workspace_bytes",
     "bb_policy_adam_step", "bb_policy_ppo_step", "bb_policy_ppo_step_workspace_bytes",
     "bb_set_action", "bb_trigger_reset", "bb_export",
@@ -161,6 +162,10 @@ def load():
         "bb_policy_ppo_grad": (ctypes.c_int, [ctypes.POINTER(PolicyWeights), i32, i32, ctypes.POINTER(PpoBatch),
                                               ctypes.POINTER(PpoCoef), ctypes.POINTER(PolicyGrads), vp, vp, i64, vp]),
         "bb_policy_ppo_grad_workspace_bytes": (i64, [i64]),
+        "bb_policy_ppo_grad_wide": (ctypes.c_int, [ctypes.POINTER(PolicyWeights), i32, i32, i32,
+                                                   ctypes.POINTER(PpoBatch), ctypes.POINTER(PpoCoef),
+                                                   ctypes.POINTER(PolicyGrads), vp, vp, i64, vp]),
+        "bb_policy_ppo_grad_wide_workspace_bytes": (i64, [i32, i64]),
         "bb_policy_advantages": (ctypes.c_int, [i32, i32, ctypes.POINTER(AdvBatch), ctypes.POINTER(RunningStatsPtrs),
                                                 ctypes.POINTER(RunningStatsPtrs), ctypes.c_double, ctypes.c_double,
                                                 vp, vp, i64, vp]),

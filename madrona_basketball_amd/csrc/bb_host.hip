@@ -1039,6 +1039,58 @@ int bb_policy_ppo_grad(const bb_policy_weights *w, int32_t exec_mode, int32_t gp
     return BB_OK;
 }
 
+int64_t bb_policy_ppo_grad_wide_workspace_bytes(int32_t in_dim, int64_t m)
+{
+    return bb::ppo_grad_wide_workspace_bytes(in_dim, m);
+}
+
+int bb_policy_ppo_grad_wide(const bb_policy_weights *w, int32_t in_dim, int32_t exec_mode, int32_t gpu_id,
+                            const bb_ppo_batch *batch, const bb_ppo_coef *coef, const bb_policy_grads *grads,
+                            float *loss4, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!bb::pol_wide_width(in_dim))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_grad_wide: in_dim must be 184, 264, 344 or 424");
+    if (!w || !batch || !coef || !grads || !loss4)
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_grad_wide: a NULL argument");
+    const void *req[] = {w->obs_mean, w->obs_inv, w->w1, w->b1, w->ln1_w, w->ln1_b, w->w2, w->b2, w->ln2_w, w->ln2_b,
+                         w->head_w, w->head_b, batch->obs, batch->actions, batch->log_prob, batch->value,
+                         batch->advantages, batch->returns, grads->w1, grads->b1, grads->ln1_w, grads->ln1_b,
+                         grads->w2, grads->b2, grads->ln2_w, grads->ln2_b, grads->head_w, grads->head_b};
+    for (const void *ptr : req) {
+        if (!ptr)
+            return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_grad_wide: a weight, batch or gradient pointer is NULL");
+        if (((uintptr_t)ptr) & 3u) return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_grad_wide: a misaligned pointer");
+    }
+    if ((((uintptr_t)batch->obs) & 15u) || (((uintptr_t)w->w1) & 15u) || (((uintptr_t)w->w2) & 15u) ||
+        (((uintptr_t)w->head_w) & 15u) || (((uintptr_t)batch->idx) & 7u))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_grad_wide: obs and the weight matrices must be 16-byte "
+                                        "aligned, idx 8-byte aligned");
+    if (batch->rows <= 0 || batch->m <= 0 || (!batch->idx && batch->m > batch->rows))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_grad_wide: rows and m must be positive (m <= rows without idx)");
+    bb::PpoGradArgs a{};
+    a.w = bb::PolicyWeights{w->obs_mean, w->obs_inv, w->w1, w->b1, w->ln1_w, w->ln1_b,
+                            w->w2, w->b2, w->ln2_w, w->ln2_b, w->head_w, w->head_b};
+    a.obs = batch->obs; a.actions = batch->actions; a.log_prob = batch->log_prob; a.value = batch->value;
+    a.adv = batch->advantages; a.ret = batch->returns; a.idx = batch->idx; a.rows = batch->rows; a.m = batch->m;
+    a.clip = coef->clip_coef; a.vf_coef = coef->vf_coef; a.ent_coef = coef->ent_coef;
+    a.g = bb::PolicyGrads{grads->w1, grads->b1, grads->ln1_w, grads->ln1_b, grads->w2, grads->b2, grads->ln2_w,
+                          grads->ln2_b, grads->head_w, grads->head_b};
+    a.loss4 = loss4;
+    if (exec_mode == BB_EXEC_CPU) {
+        bb::host_ppo_grad_wide(a, in_dim);
+        return BB_OK;
+    }
+    if (exec_mode != BB_EXEC_CUDA) return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_grad_wide: exec_mode");
+    if (!workspace || (((uintptr_t)workspace) & 15u) ||
+        workspace_bytes < bb::ppo_grad_wide_workspace_bytes(in_dim, batch->m))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_grad_wide: the workspace is NULL, misaligned or smaller than "
+                                        "bb_policy_ppo_grad_wide_workspace_bytes(in_dim, m)");
+    DeviceGuard g(gpu_id);
+    hipError_t e = bb::launch_ppo_grad_wide(a, in_dim, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "launch wide PPO gradient kernels");
+    return BB_OK;
+}
+
 int64_t bb_policy_advantages_workspace_bytes(int64_t steps, int64_t worlds)
 {
     if (steps < 1 || worlds < 1 || steps > bb::ADV_MAX_STEPS || worlds > bb::ADV_MAX_WORLDS) return 0;

@@ -221,6 +221,12 @@ void host_ppo_grad(const PpoGradArgs &a);
 int64_t ppo_grad_workspace_bytes(int64_t m);
 // k_ppo_grad alone: the workgroups' partials into a.partial, their number into *groups
 hipError_t launch_ppo_grad_partials(const PpoGradArgs &a, hipStream_t s, int *groups);
+// The same at 184, 264, 344, 424 inputs (bb_policy_grad_wide.hip): obs [rows][in_dim],
+// W1 and its gradient [32][in_dim]; workspace of ppo_grad_wide_workspace_bytes(in_dim, m)
+// bytes (0 for another width); a.partial is not read
+hipError_t launch_ppo_grad_wide(const PpoGradArgs &a, int in_dim, void *workspace, hipStream_t s);
+void host_ppo_grad_wide(const PpoGradArgs &a, int in_dim);
+int64_t ppo_grad_wide_workspace_bytes(int in_dim, int64_t m);
 // Gradient clipping, Adam's step and the weight repack (bb_policy_step.h / bb_policy_step.hip)
 struct PolicyStepArgs;
 hipError_t launch_adam_step(const PolicyStepArgs &a, hipStream_t s);

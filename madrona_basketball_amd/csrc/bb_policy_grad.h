@@ -36,7 +36,7 @@ struct PolicyGrads {
 
 struct PpoGradArgs {
     PolicyWeights w;
-    const float *obs;        // [rows][128]
+    const float *obs;        // [rows][128] (the wide gradient: [rows][in_dim])
     const int32_t *actions;  // [rows][6]
     const float *log_prob, *value, *adv, *ret;  // [rows]
     const int64_t *idx;      // [m] rows of the minibatch, or nullptr: row i
@@ -120,18 +120,26 @@ BB_HD float ppo_dlogit(float dlp, float ent_coef, float inv_m, float p, float lq
     return (dlp * ((taken ? 1.0f : 0.0f) - p) + ent_coef * (p * (lq + H))) * inv_m;
 }
 
+// The widest first layer served (bb_policy_wide.h: 184, 264, 344, 424 inputs).
+// At in_dim inputs W1's gradient is [32][in_dim] and every later element of a
+// gradient set sits 32 (in_dim - 128) floats further on.
+constexpr int PG_IN_MAX = 424;
+BB_HD constexpr int pg_floats(int in_dim) { return PG_FLOATS + POL_HID * (in_dim - POL_IN); }
+
 // Host executor: one row's forward, loss and backward in plain loops, its
-// gradient added into acc[PG_FLOATS] (double: the cross-row sums).
-inline void ppo_grad_row_host(const PpoGradArgs &a, int64_t i, double *acc)
+// gradient added into acc[pg_floats(in_dim)] (double: the cross-row sums).
+// obs rows and W1's rows are in_dim floats.
+inline void ppo_grad_row_host(const PpoGradArgs &a, int64_t i, double *acc, int in_dim)
 {
     const int64_t src = ppo_src_row(a.idx, a.rows, a.m, i);
     if (src < 0) return;
     const PolicyWeights &W = a.w;
     const float inv_m = 1.0f / (float)a.m;
-    const float *o = a.obs + src * POL_IN;
-    float x[POL_IN], xh1[POL_HID], h1[POL_HID], xh2[POL_HID], h2[POL_HID], out[PG_HEAD_LIVE];
+    const float *o = a.obs + src * in_dim;
+    const int sh = POL_HID * (in_dim - POL_IN);  // the elements behind W1
+    float x[PG_IN_MAX], xh1[POL_HID], h1[POL_HID], xh2[POL_HID], h2[POL_HID], out[PG_HEAD_LIVE];
     float rstd1 = 0.f, rstd2 = 0.f;
-    for (int k = 0; k < POL_IN; k++) x[k] = pol_clamp((o[k] - W.obs_mean[k]) * W.obs_inv[k]);
+    for (int k = 0; k < in_dim; k++) x[k] = pol_clamp((o[k] - W.obs_mean[k]) * W.obs_inv[k]);
     const auto layer = [](const float *in, int n_in, const float *w, const float *b, const float *lw, const float *lb,
                           float *xh, float *h, float *rstd) {
         float z[POL_HID], mean = 0.f, var = 0.f;
@@ -149,7 +157,7 @@ inline void ppo_grad_row_host(const PpoGradArgs &a, int64_t i, double *acc)
             h[n] = pol_relu(xh[n] * lw[n] + lb[n]);
         }
     };
-    layer(x, POL_IN, W.w1, W.b1, W.ln1_w, W.ln1_b, xh1, h1, &rstd1);
+    layer(x, in_dim, W.w1, W.b1, W.ln1_w, W.ln1_b, xh1, h1, &rstd1);
     layer(h1, POL_HID, W.w2, W.b2, W.ln2_w, W.ln2_b, xh2, h2, &rstd2);
     for (int n = 0; n < PG_HEAD_LIVE; n++) {
         float s = W.head_b[n];
@@ -175,17 +183,17 @@ inline void ppo_grad_row_host(const PpoGradArgs &a, int64_t i, double *acc)
         for (int j = 0; j < pol_bucket(b); j++)
             dout[pol_bucket_off(b) + j] = ppo_dlogit(dlp, a.ent_coef, inv_m, p[b][j], lq[b][j], H[b], act[b] == j);
     dout[POL_LOGITS] = (a.vf_coef * dv) * inv_m;
-    acc[PG_LOSS + 0] += (double)((pg + a.vf_coef * cl) - a.ent_coef * ent) * inv_m;
-    acc[PG_LOSS + 1] += (double)pg * inv_m;
-    acc[PG_LOSS + 2] += (double)cl * inv_m;
-    acc[PG_LOSS + 3] += (double)ent * inv_m;
+    acc[sh + PG_LOSS + 0] += (double)((pg + a.vf_coef * cl) - a.ent_coef * ent) * inv_m;
+    acc[sh + PG_LOSS + 1] += (double)pg * inv_m;
+    acc[sh + PG_LOSS + 2] += (double)cl * inv_m;
+    acc[sh + PG_LOSS + 3] += (double)ent * inv_m;
     // heads, then the two Linear + LayerNorm + ReLU blocks backwards
     float d2[POL_HID], d1[POL_HID];
     for (int k = 0; k < POL_HID; k++) d2[k] = 0.f;
     for (int n = 0; n < PG_HEAD_LIVE; n++) {
-        acc[PG_HB + n] += dout[n];
+        acc[sh + PG_HB + n] += dout[n];
         for (int k = 0; k < POL_HID; k++) {
-            acc[PG_HW + n * POL_HID + k] += dout[n] * h2[k];
+            acc[sh + PG_HW + n * POL_HID + k] += dout[n] * h2[k];
             d2[k] += dout[n] * W.head_w[n * POL_HID + k];
         }
     }
@@ -212,8 +220,8 @@ inline void ppo_grad_row_host(const PpoGradArgs &a, int64_t i, double *acc)
             }
         }
     };
-    back(d2, h2, xh2, rstd2, W.ln2_w, h1, POL_HID, W.w2, PG_W2, PG_B2, PG_LN2W, PG_LN2B, d1);
-    back(d1, h1, xh1, rstd1, W.ln1_w, x, POL_IN, W.w1, PG_W1, PG_B1, PG_LN1W, PG_LN1B, nullptr);
+    back(d2, h2, xh2, rstd2, W.ln2_w, h1, POL_HID, W.w2, sh + PG_W2, sh + PG_B2, sh + PG_LN2W, sh + PG_LN2B, d1);
+    back(d1, h1, xh1, rstd1, W.ln1_w, x, in_dim, W.w1, PG_W1, sh + PG_B1, sh + PG_LN1W, sh + PG_LN1B, nullptr);
 }
 
 #if defined(__HIPCC__)
@@ -221,14 +229,16 @@ inline void ppo_grad_row_host(const PpoGradArgs &a, int64_t i, double *acc)
 // workgroup of 64 elements x 4 thread rows: row t adds the partials of
 // workgroups t, t + 4, ... in order, then (c0 + c1) + (c2 + c3) through
 // chain[4][64] in LDS (one barrier).  k_ppo_grad_reduce and k_ppo_step share
-// it: the same gradient bits from either.
-__device__ __forceinline__ float pg_tree_sum(const float *partial, int groups, int e, float (*chain)[64])
+// it: the same gradient bits from either.  floats: the elements of one partial
+// (k_ppo_grad_wide_reduce has two sets of partials of its own sizes).
+__device__ __forceinline__ float pg_tree_sum(const float *partial, int groups, int e, float (*chain)[64],
+                                             int floats = PG_FLOATS)
 {
     const int x = (int)threadIdx.x, t = (int)threadIdx.y;
     float s = 0.f;
-    if (e < PG_FLOATS) {
+    if (e < floats) {
 #pragma unroll 8
-        for (int w = t; w < groups; w += 4) s = s + partial[(int64_t)w * PG_FLOATS + e];
+        for (int w = t; w < groups; w += 4) s = s + partial[(int64_t)w * floats + e];
     }
     chain[t][x] = s;
     __syncthreads();

@@ -47,4 +47,35 @@ inline void policy_row_host_wide(const PolicyArgs &a, int in_dim, int64_t r)
     policy_row_host_rest(a, r, h1);
 }
 
+#if defined(__HIPCC__)
+// Thread tid of nt copies its share of the weights into a workgroup's LDS
+// image L (k_policy_wide's PolicyWideLds<IN>, k_ppo_grad_wide's): w1[32][32 NC
+// + 4] with zero columns from IN on, norm[2][32 NC], and PolicyLdsWeights' w2,
+// wh and cst.  The caller orders the writes before their first read.
+template <int IN, class LW>
+__device__ __forceinline__ void policy_wide_weights_to_lds(LW &L, const PolicyWeights &W, int tid, int nt)
+{
+    constexpr int NC = pol_wide_chunks(IN), G = IN / 4, GP = 8 * NC + 1;  // float4 groups per row: read, written
+    for (int i = tid; i < 32 * GP; i += nt) {
+        const int n = i / GP, g = i % GP;
+        float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (g < G) w = ((const float4 *)W.w1)[n * G + g];
+        *(float4 *)&L.w1[n][4 * g] = w;
+    }
+    for (int k = tid; k < 32 * NC; k += nt) {
+        L.norm[0][k] = k < IN ? W.obs_mean[k] : 0.f;
+        L.norm[1][k] = k < IN ? W.obs_inv[k] : 0.f;
+    }
+    for (int i = tid; i < 32 * 8; i += nt) {  // W2, head_w [32][32] as float4
+        const int n = i >> 3, k = 4 * (i & 7);
+        *(float4 *)&L.w2[k >> 3][n][k & 7] = ((const float4 *)W.w2)[i];
+        *(float4 *)&L.wh[k >> 3][n][k & 7] = ((const float4 *)W.head_w)[i];
+    }
+    for (int k = tid; k < 7 * 32; k += nt) {
+        const float *src[7] = {W.b1, W.ln1_w, W.ln1_b, W.b2, W.ln2_w, W.ln2_b, W.head_b};
+        L.cst[k >> 5][k & 31] = src[k >> 5][k & 31];
+    }
+}
+#endif
+
 }  // namespace bb

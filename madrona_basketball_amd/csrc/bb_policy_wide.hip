@@ -55,31 +55,6 @@ struct PolicyWideLds {
 };
 static_assert(sizeof(PolicyWideLds<424>) <= 160 * 1024, "one workgroup's LDS");
 
-template <int IN>
-__device__ __forceinline__ void policy_wide_weights_to_lds(PolicyWideLds<IN> &L, const PolicyWeights &W, int tid, int nt)
-{
-    constexpr int NC = PolicyWideLds<IN>::NC, G = IN / 4, GP = 8 * NC + 1;  // float4 groups per row: read, written
-    for (int i = tid; i < 32 * GP; i += nt) {
-        const int n = i / GP, g = i % GP;
-        float4 w = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (g < G) w = ((const float4 *)W.w1)[n * G + g];
-        *(float4 *)&L.w1[n][4 * g] = w;
-    }
-    for (int k = tid; k < 32 * NC; k += nt) {
-        L.norm[0][k] = k < IN ? W.obs_mean[k] : 0.f;
-        L.norm[1][k] = k < IN ? W.obs_inv[k] : 0.f;
-    }
-    for (int i = tid; i < 32 * 8; i += nt) {  // W2, head_w [32][32] as float4
-        const int n = i >> 3, k = 4 * (i & 7);
-        *(float4 *)&L.w2[k >> 3][n][k & 7] = ((const float4 *)W.w2)[i];
-        *(float4 *)&L.wh[k >> 3][n][k & 7] = ((const float4 *)W.head_w)[i];
-    }
-    for (int k = tid; k < 7 * 32; k += nt) {
-        const float *src[7] = {W.b1, W.ln1_w, W.ln1_b, W.b2, W.ln2_w, W.ln2_b, W.head_b};
-        L.cst[k >> 5][k & 31] = src[k >> 5][k & 31];
-    }
-}
-
 // A lane's 8 floats of one chunk.
 struct WideChunk {
     float4 lo, hi;

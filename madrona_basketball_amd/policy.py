@@ -5,7 +5,10 @@ by one gfx950 kernel (bb_policy_forward, csrc/bb_policy.hip; at the 184 / 264 /
 csrc/bb_policy_wide.hip) that writes its actions straight into the simulator's
 action tensor -- the `actions, log_probs, values = agent(obs)` +
 `actions[:, i] = a` pair of scripts/ppo.py:67 / scripts/env.py:147 without a
-round trip through torch.  The rollout and the PPO update are 128-wide only.
+round trip through torch.  The wide networks also have the minibatch loss and
+gradient in one call (FusedPolicy.ppo_grad_wide, bb_policy_ppo_grad_wide,
+csrc/bb_policy_grad_wide.hip); the rollout, the advantage phase and the fused
+clip + Adam step are 128-wide only.
 
 FusedPolicy.from_agent(agent) snapshots the weights of any torch module with
 the reference Agent's layout (obs_norm.mean/var, backbone Linear/LayerNorm,
@@ -281,11 +284,54 @@ class FusedPolicy:
         a.critic.bias.grad.copy_(hb[LOGITS:LOGITS + 1])
         return loss4
 
-    def _ppo_args(self, obs, actions, log_prob, value, advantages, returns, idx):
-        """ppo_grad's checks of the batch: its descriptor and M."""
+    def ppo_grad_wide(self, obs: torch.Tensor, actions: torch.Tensor, log_prob: torch.Tensor, value: torch.Tensor,
+                      advantages: torch.Tensor, returns: torch.Tensor, idx: torch.Tensor = None,
+                      clip_coef: float = 0.2, vf_coef: float = 1.0, ent_coef: float = 0.01) -> torch.Tensor:
+        """ppo_grad for a policy of 184, 264, 344 or 424 inputs (the 2v2 to 5v5
+        games), bb_policy_ppo_grad_wide: the same contract with obs float32
+        [R, in_dim] -- the rows `idx` gathered by the kernels, the gradient left in
+        .grad of the agent's 12 parameters (backbone[0].weight.grad is [32, in_dim]),
+        head_grad kept, float32 [4] returned on the device, no host
+        synchronisation.  It is the one fused piece of the wide update; a training
+        step at these widths is
+            ppo_grad_wide(...); clip_grad_norm_(agent.parameters(), c);
+            optimizer.step(); refresh()
+        with torch's own clipping and Adam (optimizer_step, ppo_minibatch,
+        ppo_update, compute_advantages and rollout remain 128-wide)."""
+        if self.in_dim == IN:
+            raise ValueError("ppo_grad_wide serves the 184, 264, 344 and 424-input policies; this one has 128 inputs: "
+                             "use ppo_grad")
+        width = self.in_dim
+        batch, m = self._ppo_args(obs, actions, log_prob, value, advantages, returns, idx, width)
+        direct = self._params(True, width)[:8]
+        dev, f32, a = self.device, torch.float32, self.agent
+        lib = _lib.load()
+        cuda = dev.type == "cuda"
+        need = lib.bb_policy_ppo_grad_wide_workspace_bytes(width, m) if cuda else 0
+        if getattr(self, "_ppo_ws", None) is None or self._ppo_ws.numel() * 4 < need:
+            self._ppo_ws = torch.empty((max(need, 4) // 4,), dtype=f32, device=dev)
+        if getattr(self, "head_grad", None) is None:
+            self.head_grad = (torch.zeros((HEAD, HID), dtype=f32, device=dev), torch.zeros((HEAD,), dtype=f32, device=dev))
+        hw, hb = self.head_grad
+        loss4 = torch.empty((4,), dtype=f32, device=dev)
+        coef = _lib.PpoCoef(float(clip_coef), float(vf_coef), float(ent_coef))
+        grads = _lib.PolicyGrads(*[p.grad.data_ptr() for p in direct], hw.data_ptr(), hb.data_ptr())
+        _lib.check(lib.bb_policy_ppo_grad_wide(
+            ctypes.byref(self._w), width, int(ExecMode.CUDA if cuda else ExecMode.CPU),
+            dev.index if dev.index is not None else -1, ctypes.byref(batch), ctypes.byref(coef), ctypes.byref(grads),
+            ctypes.c_void_p(loss4.data_ptr()), ctypes.c_void_p(self._ppo_ws.data_ptr() if cuda else None),
+            need, self._stream()), "policy_ppo_grad_wide")
+        a.actor.weight.grad.copy_(hw[:LOGITS])
+        a.critic.weight.grad.copy_(hw[LOGITS:LOGITS + 1])
+        a.actor.bias.grad.copy_(hb[:LOGITS])
+        a.critic.bias.grad.copy_(hb[LOGITS:LOGITS + 1])
+        return loss4
+
+    def _ppo_args(self, obs, actions, log_prob, value, advantages, returns, idx, width: int = IN):
+        """ppo_grad's checks of the batch (obs rows of `width` floats): its descriptor and M."""
         dev, f32 = self.device, torch.float32
-        if obs.dim() != 2 or obs.shape[1] != IN or obs.dtype != f32 or not obs.is_contiguous():
-            raise ValueError("obs must be a contiguous float32 [rows, 128] tensor")
+        if obs.dim() != 2 or obs.shape[1] != width or obs.dtype != f32 or not obs.is_contiguous():
+            raise ValueError(f"obs must be a contiguous float32 [rows, {width}] tensor")
         rows = obs.shape[0]
         if tuple(actions.shape) != (rows, 6) or actions.dtype != torch.int32 or not actions.is_contiguous():
             raise ValueError("actions must be a contiguous int32 [rows, 6] tensor")
@@ -305,17 +351,17 @@ class FusedPolicy:
                               rows, m)
         return batch, m
 
-    def _params(self, make_grads: bool) -> list:
-        """The agent's 12 parameters in agent.parameters() order (w1 b1 ln1_w ln1_b
-        w2 b2 ln2_w ln2_b actor.w actor.b critic.w critic.b), float32 on the
-        policy's device, each with a contiguous .grad (made if make_grads)."""
+    def _params(self, make_grads: bool, width: int = IN) -> list:
+        """The agent's 12 parameters in agent.parameters() order (w1 [32, width] b1
+        ln1_w ln1_b w2 b2 ln2_w ln2_b actor.w actor.b critic.w critic.b), float32 on
+        the policy's device, each with a contiguous .grad (made if make_grads)."""
         a, dev = self.agent, self.device
         lin = [mod for mod in a.backbone if isinstance(mod, torch.nn.Linear)]
         lns = [mod for mod in a.backbone if isinstance(mod, torch.nn.LayerNorm)]
         ps = [lin[0].weight, lin[0].bias, lns[0].weight, lns[0].bias, lin[1].weight, lin[1].bias, lns[1].weight,
               lns[1].bias, a.actor.weight, a.actor.bias, a.critic.weight, a.critic.bias]
-        if tuple(ps[0].shape) != (HID, IN) or tuple(ps[4].shape) != (HID, HID) or a.actor.out_features != LOGITS:
-            raise ValueError("FusedPolicy supports the reference configuration: input 128, num_channels 32, "
+        if tuple(ps[0].shape) != (HID, width) or tuple(ps[4].shape) != (HID, HID) or a.actor.out_features != LOGITS:
+            raise ValueError(f"FusedPolicy supports the reference configuration: input {width}, num_channels 32, "
                              "num_layers 2, buckets [2, 8, 3, 2, 2, 2] (scripts/env.py:107)")
         for p in ps:
             if p.device != dev or p.dtype != torch.float32:
