@@ -402,6 +402,17 @@ int bb_policy_advantages(int32_t exec_mode, int32_t gpu_id, const bb_adv_batch *
                          double gae_lambda, float *out4, void *workspace, int64_t workspace_bytes, void *stream);
 int64_t bb_policy_advantages_workspace_bytes(int64_t steps, int64_t worlds);
 
+/* bb_policy_advantages for observation rows of in_dim = 184, 264, 344 or 424
+ * floats: batch->obs is float [steps][worlds][in_dim], obs_norm holds in_dim
+ * statistics; everything else, every formula and every check as above.
+ * workspace: bb_policy_advantages_wide_workspace_bytes(in_dim, steps, worlds)
+ * bytes (0 for another in_dim).  BB_ERR_INVALID_ARG (nothing launched) for any
+ * other in_dim. */
+int bb_policy_advantages_wide(int32_t in_dim, int32_t exec_mode, int32_t gpu_id, const bb_adv_batch *batch,
+                              const bb_running_stats *value_norm, const bb_running_stats *obs_norm, double gamma,
+                              double gae_lambda, float *out4, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t bb_policy_advantages_wide_workspace_bytes(int32_t in_dim, int64_t steps, int64_t worlds);
+
 /* What follows loss.backward() in one minibatch of update_policy
  * (scripts/ppo.py:214-215): torch.nn.utils.clip_grad_norm_, then
  * torch.optim.Adam's step with its defaults (no weight decay, no amsgrad),
@@ -451,6 +462,28 @@ int bb_policy_ppo_step(const bb_policy_weights *w, int32_t exec_mode, int32_t gp
                        const bb_adam_state *state, const bb_adam_hyper *hyper, float *out6, void *workspace,
                        int64_t workspace_bytes, void *stream);
 int64_t bb_policy_ppo_step_workspace_bytes(int64_t m);
+
+/* The same two entries for the networks of in_dim = 184, 264, 344 or 424
+ * inputs (bb_policy_ppo_grad_wide's).  params->w1, grads->w1 and w->w1 are
+ * [32][in_dim]; exp_avg / exp_avg_sq are float [E], E = 32 in_dim + 1876 (7764,
+ * 10324, 12884, 15444), in the same tensor order: w1 first, every later offset
+ * the 128-wide one plus 32 (in_dim - 128).  Same math, same checks, same
+ * results (out2 / out6).  bb_policy_ppo_step_wide runs
+ * bb_policy_ppo_grad_wide's two passes, then the step, and gives the bits of
+ * bb_policy_ppo_grad_wide followed by bb_policy_adam_step_wide.  workspace:
+ * bb_policy_ppo_step_wide_workspace_bytes(in_dim, m) bytes on the device,
+ * 16-byte aligned (CUDA mode): bb_policy_ppo_grad_wide's, then the unclipped
+ * gradient and the partial sums of squares; 0 for another in_dim or m <= 0.
+ * The ticket is not used.  BB_ERR_INVALID_ARG (nothing launched) for any other
+ * in_dim. */
+int bb_policy_adam_step_wide(const bb_policy_weights *w, int32_t in_dim, int32_t exec_mode, int32_t gpu_id,
+                             const bb_policy_params *params, const bb_policy_params *grads, const bb_adam_state *state,
+                             const bb_adam_hyper *hyper, float *out2, void *stream);
+int bb_policy_ppo_step_wide(const bb_policy_weights *w, int32_t in_dim, int32_t exec_mode, int32_t gpu_id,
+                            const bb_ppo_batch *batch, const bb_ppo_coef *coef, const bb_policy_params *params,
+                            const bb_policy_params *grads, const bb_adam_state *state, const bb_adam_hyper *hyper,
+                            float *out6, void *workspace, int64_t workspace_bytes, void *stream);
+int64_t bb_policy_ppo_step_wide_workspace_bytes(int32_t in_dim, int64_t m);
 
 int bb_set_action(bb_sim *sim, int32_t world_idx, int32_t agent_idx, int32_t move_speed,
                   int32_t move_angle, int32_t rotate, int32_t grab, int32_t pass,

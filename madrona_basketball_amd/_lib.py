@@ -46,7 +46,9 @@ ABI_SYMBOLS = [
     "bb_policy_ppo_grad", "bb_policy_ppo_grad_workspace_bytes",
     "bb_policy_ppo_grad_wide", "bb_policy_ppo_grad_wide_workspace_bytes",
     "bb_policy_advantages", "bb_policy_advantages_workspace_bytes",
+    "bb_policy_advantages_wide", "bb_policy_advantages_wide_workspace_bytes",
     "bb_policy_adam_step", "bb_policy_ppo_step", "bb_policy_ppo_step_workspace_bytes",
+    "bb_policy_adam_step_wide", "bb_policy_ppo_step_wide", "bb_policy_ppo_step_wide_workspace_bytes",
     "bb_set_action", "bb_trigger_reset", "bb_export",
     "bb_num_worlds", "bb_num_agents", "bb_exec_mode", "bb_algorithmic_bytes_per_world",
     "bb_rollout_policy_path", "bb_rollout_policy_bytes", "bb_step_staged_path", "bb_step_staged_bytes",
@@ -178,6 +180,19 @@ def load():
                                               ctypes.POINTER(PolicyParams), ctypes.POINTER(AdamStatePtrs),
                                               ctypes.POINTER(AdamHyper), vp, vp, i64, vp]),
         "bb_policy_ppo_step_workspace_bytes": (i64, [i64]),
+        "bb_policy_advantages_wide": (ctypes.c_int, [i32, i32, i32, ctypes.POINTER(AdvBatch),
+                                                     ctypes.POINTER(RunningStatsPtrs), ctypes.POINTER(RunningStatsPtrs),
+                                                     ctypes.c_double, ctypes.c_double, vp, vp, i64, vp]),
+        "bb_policy_advantages_wide_workspace_bytes": (i64, [i32, i64, i64]),
+        "bb_policy_adam_step_wide": (ctypes.c_int, [ctypes.POINTER(PolicyWeights), i32, i32, i32,
+                                                    ctypes.POINTER(PolicyParams), ctypes.POINTER(PolicyParams),
+                                                    ctypes.POINTER(AdamStatePtrs), ctypes.POINTER(AdamHyper), vp, vp]),
+        "bb_policy_ppo_step_wide": (ctypes.c_int, [ctypes.POINTER(PolicyWeights), i32, i32, i32,
+                                                   ctypes.POINTER(PpoBatch), ctypes.POINTER(PpoCoef),
+                                                   ctypes.POINTER(PolicyParams), ctypes.POINTER(PolicyParams),
+                                                   ctypes.POINTER(AdamStatePtrs), ctypes.POINTER(AdamHyper), vp, vp, i64,
+                                                   vp]),
+        "bb_policy_ppo_step_wide_workspace_bytes": (i64, [i32, i64]),
         "bb_set_action": (ctypes.c_int, [vp, i32, i32, i32, i32, i32, i32, i32, i32, vp]),
         "bb_trigger_reset": (ctypes.c_int, [vp, i32, vp]),
         "bb_export": (ctypes.c_int, [vp, i32, ctypes.POINTER(vp), ctypes.POINTER(i32),

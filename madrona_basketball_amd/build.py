@@ -27,7 +27,8 @@ KERNEL_FLAGS = ["-mllvm", "-disable-machine-licm"]
 # (r02v: 141.1 / 310.5 us), N = 4 and 8 were slower.
 MAX_ILP = ["-mllvm", "-amdgpu-sched-strategy=max-ilp"]
 N_FLAGS = {2: MAX_ILP}
-# bb_policy_grad.hip, bb_policy_grad_wide.hip, bb_advantages.hip, bb_policy_step.hip: no packed fp32 arithmetic (v_pk_add / mul / fma_f32) on
+# bb_policy_grad.hip, bb_policy_grad_wide.hip, bb_advantages.hip, bb_advantages_wide.hip, bb_policy_step.hip,
+# bb_policy_step_wide.hip: no packed fp32 arithmetic (v_pk_add / mul / fma_f32) on
 # the device, every float op its own instruction (the host pass does not know
 # the feature and says that it ignores it).
 NO_PK_F32 = ["-Xclang", "-target-feature", "-Xclang", "-packed-fp32-ops"]
@@ -40,10 +41,13 @@ UNITS = ([("bb_kernels.hip", [f"-DBB_N={n}", *KERNEL_FLAGS, *N_FLAGS.get(n, [])]
             ("bb_policy_grad.hip", NO_PK_F32, "bb_policy_grad.o"),
             ("bb_policy_grad_wide.hip", NO_PK_F32, "bb_policy_grad_wide.o"),
             ("bb_advantages.hip", NO_PK_F32, "bb_advantages.o"),
-            ("bb_policy_step.hip", NO_PK_F32, "bb_policy_step.o")])
+            ("bb_advantages_wide.hip", NO_PK_F32, "bb_advantages_wide.o"),
+            ("bb_policy_step.hip", NO_PK_F32, "bb_policy_step.o"),
+            ("bb_policy_step_wide.hip", NO_PK_F32, "bb_policy_step_wide.o")])
 SOURCES = sorted({u[0] for u in UNITS})
 HEADERS = ["bb_math.h", "bb_rng.h", "bb_sim.h", "bb_launch.h", "bb_policy.h", "bb_policy_dev.h", "bb_policy_wide.h",
-           "bb_policy_grad.h", "bb_policy_grad_dev.h", "bb_advantages.h", "bb_policy_step.h"]
+           "bb_policy_grad.h", "bb_policy_grad_dev.h", "bb_advantages.h", "bb_advantages_dev.h", "bb_policy_step.h",
+           "bb_policy_step_wide.h"]
 ARCH = os.environ.get("BB_OFFLOAD_ARCH", "gfx950")
 
 # -ffp-contract=off: every float op rounds on its own (bit parity host <-> gfx950)

@@ -25,6 +25,7 @@
 namespace bb {
 
 constexpr int ADV_OBS = 128;        // observation columns
+constexpr int ADV_OBS_MAX = 424;    // the widest rows served (bb_advantages_wide.hip: 184, 264, 344, 424)
 constexpr int ADV_THREADS = 256;    // k_adv_scan: 4 waves
 constexpr int ADV_GAE_GROUPS = 64;  // GAE role: at most 64 workgroups of 256 worlds, grid-stride
 constexpr int ADV_OBS_LOADS = 8;    // observation role: 16-byte loads in flight per lane (2 rows per wave load)
@@ -64,6 +65,22 @@ BB_HD AdvGrid adv_grid(int32_t steps, int64_t worlds)
     const int64_t g = (worlds + ADV_THREADS - 1) / ADV_THREADS;
     const int64_t o = (worlds * steps + ADV_OBS_ROWS - 1) / ADV_OBS_ROWS;
     return {(int)(g < ADV_GAE_GROUPS ? g : ADV_GAE_GROUPS), (int)(o < ADV_OBS_GROUPS ? o : ADV_OBS_GROUPS)};
+}
+
+// The observation role at 184, 264, 344, 424 columns (bb_advantages_wide.hip):
+// a workgroup pass is RP whole rows, thread t the 16 bytes at 16 t of it (RP
+// IN / 4 threads: 506, 990, 946, 954, rounded up to whole waves), ADV_OBS_LOADS
+// passes per batch.  Wide grid rule: the GAE role as adv_grid has it; the
+// observation role min(512, ceil(K W / (8 RP))) workgroups, grid-stride over
+// batches of 8 RP = 88, 120, 88, 72 rows.  Partial stride: mean[IN], M2[IN], n.
+BB_HD constexpr int adv_wide_rp(int in_dim) { return in_dim == 184 ? 11 : in_dim == 264 ? 15 : in_dim == 344 ? 11 : 9; }
+BB_HD constexpr int adv_wide_threads(int in_dim) { return (adv_wide_rp(in_dim) * (in_dim / 4) + 63) / 64 * 64; }
+BB_HD constexpr int adv_wide_ws_obs(int in_dim) { return 2 * in_dim + 8; }
+BB_HD AdvGrid adv_wide_grid(int in_dim, int32_t steps, int64_t worlds)
+{
+    const int64_t batch = ADV_OBS_LOADS * adv_wide_rp(in_dim);
+    const int64_t o = (worlds * steps + batch - 1) / batch;
+    return {adv_grid(steps, worlds).gae, (int)(o < ADV_OBS_GROUPS ? o : ADV_OBS_GROUPS)};
 }
 
 // agent.py:31-34, unnorm with clamp 5: mean + sqrt(var) * clamp(x)

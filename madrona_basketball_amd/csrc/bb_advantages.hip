@@ -30,82 +30,12 @@
 // The order of every sum is fixed by the shape alone: two calls on the same
 // inputs give the same bits.
 #include <hip/hip_runtime.h>
-#include "bb_advantages.h"
+#include "bb_advantages_dev.h"
 #include "bb_launch.h"
 
 namespace bb {
 
-constexpr int ADV_GAE_BLOCK = 8;  // steps whose loads are issued together
 constexpr int ADV_FIN_THREADS = ADV_FIN_COLS * ADV_FIN_CHAINS;
-
-__device__ __forceinline__ double adv_wave_sum(double x)
-{
-#pragma unroll
-    for (int m = 1; m < 64; m <<= 1) x = x + __shfl_xor(x, m);
-    return x;
-}
-
-// red: [4 waves][7] doubles
-__device__ void adv_gae_role(const AdvArgs &a, int group, int groups, double *red)
-{
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int K = a.steps;
-    const int64_t W = a.worlds;
-    const float m = (float)a.vn.mean[0], sq = __builtin_sqrtf((float)a.vn.var[0] + 1e-5f);
-    const double shift = (double)m;
-    double sum[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};  // v, Rt, A: sum, sum of squares
-    int worlds = 0;
-    for (int64_t w = (int64_t)group * ADV_THREADS + tid; w < W; w += (int64_t)groups * ADV_THREADS) {
-        float nxt = adv_unnorm(m, sq, a.next_value[w]);
-        float nnt = 1.f - a.done[(int64_t)(K - 1) * W + w];
-        float last = 0.f;
-        for (int t1 = K; t1 > 0; t1 -= ADV_GAE_BLOCK) {
-            float val[ADV_GAE_BLOCK], rew[ADV_GAE_BLOCK], dn[ADV_GAE_BLOCK];
-#pragma unroll
-            for (int i = 0; i < ADV_GAE_BLOCK; i++) {  // steps below 0 re-read row 0 and are not used
-                const int t = t1 - 1 - i;
-                const int64_t at = (int64_t)(t < 0 ? 0 : t) * W + w;
-                val[i] = a.value[at]; rew[i] = a.reward[at]; dn[i] = a.done[at];
-            }
-#pragma unroll
-            for (int i = 0; i < ADV_GAE_BLOCK; i++) {
-                const int t = t1 - 1 - i;
-                if (t >= 0) {
-                    const float v = adv_unnorm(m, sq, val[i]);
-                    const float adv = adv_gae_step(rew[i], v, nxt, nnt, a.gamma, a.gl, &last);
-                    const float rt = adv + v;
-                    const int64_t at = (int64_t)t * W + w;
-                    a.adv[at] = adv;
-                    a.ret[at] = rt;
-                    const double dv = (double)v - shift, dr = (double)rt - shift, da = (double)adv;
-                    sum[0] = sum[0] + dv; sum[1] = sum[1] + dv * dv;
-                    sum[2] = sum[2] + dr; sum[3] = sum[3] + dr * dr;
-                    sum[4] = sum[4] + da; sum[5] = sum[5] + da * da;
-                    nxt = v;
-                    nnt = 1.f - dn[i];
-                }
-            }
-        }
-        worlds++;
-    }
-#pragma unroll
-    for (int k = 0; k < 6; k++) {
-        const double s = adv_wave_sum(sum[k]);
-        if (lane == 0) red[wave * 7 + k] = s;
-    }
-    const double n = adv_wave_sum((double)worlds * (double)K);
-    if (lane == 0) red[wave * 7 + 6] = n;
-    __syncthreads();
-    if (tid < 3) {
-        double s = 0.0, q = 0.0, cnt = 0.0;
-        for (int w = 0; w < ADV_THREADS / 64; w++) {
-            s = s + red[w * 7 + 2 * tid]; q = q + red[w * 7 + 2 * tid + 1]; cnt = cnt + red[w * 7 + 6];
-        }
-        const Moments mo = adv_moments(cnt, tid < 2 ? shift : 0.0, s, q);
-        double *dst = a.ws + ADV_WS_HEAD + group * ADV_WS_GAE + 3 * tid;
-        dst[0] = mo.n; dst[1] = mo.mean; dst[2] = mo.m2;
-    }
-}
 
 // red: [4 waves][2][128] sums, then [4] row counts
 __device__ void adv_obs_role(const AdvArgs &a, int group, int groups, double *red)
@@ -249,13 +179,18 @@ int64_t advantages_workspace_bytes(int32_t steps, int64_t worlds)
 hipError_t launch_advantages(const AdvArgs &a, hipStream_t s)
 {
     const AdvGrid g = adv_grid(a.steps, a.worlds);
-    const int64_t n = a.worlds * a.steps;
     hipLaunchKernelGGL(k_adv_scan, dim3(g.gae + g.obs), dim3(ADV_THREADS), 0, s, a, g.gae, g.obs);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(k_adv_finish, dim3(ADV_OBS / ADV_FIN_COLS + 1), dim3(ADV_FIN_THREADS), 0, s, a, g.gae, g.obs);
     e = hipGetLastError();
     if (e != hipSuccess) return e;
+    return launch_adv_norm(a, s);
+}
+
+hipError_t launch_adv_norm(const AdvArgs &a, hipStream_t s)
+{
+    const int64_t n = a.worlds * a.steps;
     const int vec = ((((uintptr_t)a.adv) | ((uintptr_t)a.ret)) & 15u) == 0;
     hipLaunchKernelGGL(k_adv_norm, dim3((unsigned)(((n + 3) / 4 + 255) / 256)), dim3(256), 0, s, a.adv, a.ret, n,
                        (const float *)a.ws, vec);
@@ -263,7 +198,8 @@ hipError_t launch_advantages(const AdvArgs &a, hipStream_t s)
 }
 
 // Host executor: scalar loops in the reference's order, every sum in double.
-void host_advantages(const AdvArgs &a)
+// in_dim: the observation width (128, or bb_advantages_wide.hip's).
+void host_advantages(const AdvArgs &a, int in_dim)
 {
     const int K = a.steps;
     const int64_t W = a.worlds, rows = W * K;
@@ -285,15 +221,15 @@ void host_advantages(const AdvArgs &a)
             nnt = 1.f - a.done[at];
         }
     }
-    double S[ADV_OBS], Q[ADV_OBS], sh[ADV_OBS];
-    for (int c = 0; c < ADV_OBS; c++) { S[c] = 0.0; Q[c] = 0.0; sh[c] = (double)(float)a.on.mean[c]; }
+    double S[ADV_OBS_MAX], Q[ADV_OBS_MAX], sh[ADV_OBS_MAX];
+    for (int c = 0; c < in_dim; c++) { S[c] = 0.0; Q[c] = 0.0; sh[c] = (double)(float)a.on.mean[c]; }
     for (int64_t r = 0; r < rows; r++)
-        for (int c = 0; c < ADV_OBS; c++) {
-            const double d = (double)a.obs[r * ADV_OBS + c] - sh[c];
+        for (int c = 0; c < in_dim; c++) {
+            const double d = (double)a.obs[r * in_dim + c] - sh[c];
             S[c] += d; Q[c] += d * d;
         }
     double count = a.on.count[0];
-    for (int c = 0; c < ADV_OBS; c++) {
+    for (int c = 0; c < in_dim; c++) {
         count = a.on.count[0];
         adv_update(a.on.mean[c], a.on.var[c], count, adv_moments((double)rows, sh[c], S[c], Q[c]));
     }

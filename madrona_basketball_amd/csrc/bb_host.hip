@@ -26,6 +26,7 @@
 #include "bb_launch.h"
 #include "bb_policy_grad.h"
 #include "bb_policy_step.h"
+#include "bb_policy_step_wide.h"
 #include "bb_policy_wide.h"
 #include "bb_sim.h"
 
@@ -531,6 +532,28 @@ void host_policy_step(const PolicyStepArgs &a, bool fused)
     }
     a.out[fused ? 4 : 0] = sc.norm;
     a.out[fused ? 5 : 1] = sc.coef;
+}
+
+// The same over the wide element order (bb_policy_step_wide.h).
+void host_policy_step_wide(const PolicyStepWideArgs &a, bool fused)
+{
+    double sum = 0.0;
+    for (int s = 0; s < PS_TENSORS; s++) {
+        const StepSeg sg = step_seg_wide(a, s);
+        for (int i = 0; i < sg.len; i++) sum += (double)sg.grad[i] * (double)sg.grad[i];
+    }
+    const int64_t t = *a.s.step + 1;
+    *a.s.step = t;
+    const AdamScalars sc = adam_scalars(a.s.h, sum, t);
+    for (int s = 0; s < PS_TENSORS; s++) {
+        const StepSeg sg = step_seg_wide(a, s);
+        for (int i = 0; i < sg.len; i++) {
+            sg.grad[i] = adam_element(sc, sg.grad[i], a.s.exp_avg + sg.e0 + i, a.s.exp_avg_sq + sg.e0 + i, sg.param + i);
+            sg.packed[i] = sg.param[i];
+        }
+    }
+    a.s.out[fused ? 4 : 0] = sc.norm;
+    a.s.out[fused ? 5 : 1] = sc.coef;
 }
 
 }  // namespace bb
@@ -1097,30 +1120,35 @@ int64_t bb_policy_advantages_workspace_bytes(int64_t steps, int64_t worlds)
     return bb::advantages_workspace_bytes((int32_t)steps, worlds);
 }
 
-int bb_policy_advantages(int32_t exec_mode, int32_t gpu_id, const bb_adv_batch *batch,
-                         const bb_running_stats *value_norm, const bb_running_stats *obs_norm, double gamma,
-                         double gae_lambda, float *out4, void *workspace, int64_t workspace_bytes, void *stream)
+namespace {
+
+// bb_policy_advantages (in_dim 128) and bb_policy_advantages_wide: the checks, then either executor.
+int policy_advantages(const char *who, int32_t in_dim, int32_t exec_mode, int32_t gpu_id, const bb_adv_batch *batch,
+                      const bb_running_stats *value_norm, const bb_running_stats *obs_norm, double gamma,
+                      double gae_lambda, float *out4, void *workspace, int64_t workspace_bytes, void *stream)
 {
+    const std::string me(who);
+    const bool wide = in_dim != bb::ADV_OBS;
     if (!batch || !value_norm || !obs_norm || !out4)
-        return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: a NULL argument");
+        return fail(BB_ERR_INVALID_ARG, me + ": a NULL argument");
     const void *f32[] = {batch->obs, batch->value, batch->reward, batch->done, batch->next_value, batch->advantages,
                          batch->returns, out4};
     for (const void *ptr : f32) {
-        if (!ptr) return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: a batch or output pointer is NULL");
-        if (((uintptr_t)ptr) & 3u) return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: a misaligned pointer");
+        if (!ptr) return fail(BB_ERR_INVALID_ARG, me + ": a batch or output pointer is NULL");
+        if (((uintptr_t)ptr) & 3u) return fail(BB_ERR_INVALID_ARG, me + ": a misaligned pointer");
     }
     if (((uintptr_t)batch->obs) & 15u)
-        return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: obs must be 16-byte aligned");
+        return fail(BB_ERR_INVALID_ARG, me + ": obs must be 16-byte aligned");
     const void *f64[] = {value_norm->mean, value_norm->var, value_norm->count, obs_norm->mean, obs_norm->var,
                          obs_norm->count};
     for (const void *ptr : f64) {
-        if (!ptr) return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: a normaliser's mean, var or count is NULL");
+        if (!ptr) return fail(BB_ERR_INVALID_ARG, me + ": a normaliser's mean, var or count is NULL");
         if (((uintptr_t)ptr) & 7u)
-            return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: the normalisers' doubles must be 8-byte aligned");
+            return fail(BB_ERR_INVALID_ARG, me + ": the normalisers' doubles must be 8-byte aligned");
     }
     if (batch->steps < 1 || batch->worlds < 1 || batch->steps > bb::ADV_MAX_STEPS ||
         batch->worlds > bb::ADV_MAX_WORLDS || batch->steps * batch->worlds < 2)
-        return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: steps x worlds must be at least 2 (the unbiased "
+        return fail(BB_ERR_INVALID_ARG, me + ": steps x worlds must be at least 2 (the unbiased "
                                         "variance of one row is undefined)");
     bb::AdvArgs a{};
     a.obs = batch->obs; a.value = batch->value; a.reward = batch->reward; a.done = batch->done;
@@ -1130,19 +1158,47 @@ int bb_policy_advantages(int32_t exec_mode, int32_t gpu_id, const bb_adv_batch *
     a.gamma = (float)gamma; a.gl = (float)(gamma * gae_lambda);
     a.steps = (int32_t)batch->steps; a.worlds = batch->worlds; a.out4 = out4;
     if (exec_mode == BB_EXEC_CPU) {
-        bb::host_advantages(a);
+        bb::host_advantages(a, in_dim);
         return BB_OK;
     }
-    if (exec_mode != BB_EXEC_CUDA) return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: exec_mode");
+    if (exec_mode != BB_EXEC_CUDA) return fail(BB_ERR_INVALID_ARG, me + ": exec_mode");
     if (!workspace || (((uintptr_t)workspace) & 15u) ||
-        workspace_bytes < bb::advantages_workspace_bytes(a.steps, a.worlds))
-        return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages: the workspace is NULL, misaligned or smaller than "
-                                        "bb_policy_advantages_workspace_bytes(steps, worlds)");
+        workspace_bytes < (wide ? bb::advantages_wide_workspace_bytes(in_dim, a.steps, a.worlds)
+                                : bb::advantages_workspace_bytes(a.steps, a.worlds)))
+        return fail(BB_ERR_INVALID_ARG, me + ": the workspace is NULL, misaligned or smaller than " + me +
+                                        "_workspace_bytes()");
     a.ws = (double *)workspace;
     DeviceGuard g(gpu_id);
-    hipError_t e = bb::launch_advantages(a, (hipStream_t)stream);
+    hipError_t e = wide ? bb::launch_advantages_wide(a, in_dim, (hipStream_t)stream)
+                        : bb::launch_advantages(a, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "launch advantage kernels");
     return BB_OK;
+}
+
+}  // namespace
+
+int bb_policy_advantages(int32_t exec_mode, int32_t gpu_id, const bb_adv_batch *batch,
+                         const bb_running_stats *value_norm, const bb_running_stats *obs_norm, double gamma,
+                         double gae_lambda, float *out4, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    return policy_advantages("bb_policy_advantages", bb::ADV_OBS, exec_mode, gpu_id, batch, value_norm, obs_norm, gamma,
+                             gae_lambda, out4, workspace, workspace_bytes, stream);
+}
+
+int64_t bb_policy_advantages_wide_workspace_bytes(int32_t in_dim, int64_t steps, int64_t worlds)
+{
+    if (steps < 1 || worlds < 1 || steps > bb::ADV_MAX_STEPS || worlds > bb::ADV_MAX_WORLDS) return 0;
+    return bb::advantages_wide_workspace_bytes(in_dim, (int32_t)steps, worlds);
+}
+
+int bb_policy_advantages_wide(int32_t in_dim, int32_t exec_mode, int32_t gpu_id, const bb_adv_batch *batch,
+                              const bb_running_stats *value_norm, const bb_running_stats *obs_norm, double gamma,
+                              double gae_lambda, float *out4, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!bb::pol_wide_width(in_dim))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_advantages_wide: in_dim must be 184, 264, 344 or 424");
+    return policy_advantages("bb_policy_advantages_wide", in_dim, exec_mode, gpu_id, batch, value_norm, obs_norm, gamma,
+                             gae_lambda, out4, workspace, workspace_bytes, stream);
 }
 
 namespace {
@@ -1259,6 +1315,88 @@ int bb_policy_ppo_step(const bb_policy_weights *w, int32_t exec_mode, int32_t gp
     DeviceGuard g(gpu_id);
     hipError_t e = bb::launch_ppo_step(ga, a, workspace, (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "launch PPO step kernels");
+    return BB_OK;
+}
+
+int bb_policy_adam_step_wide(const bb_policy_weights *w, int32_t in_dim, int32_t exec_mode, int32_t gpu_id,
+                             const bb_policy_params *params, const bb_policy_params *grads, const bb_adam_state *state,
+                             const bb_adam_hyper *hyper, float *out2, void *stream)
+{
+    if (!bb::pol_wide_width(in_dim))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_adam_step_wide: in_dim must be 184, 264, 344 or 424");
+    bb::PolicyStepWideArgs a{};
+    a.in_dim = in_dim;
+    const int rc = policy_step_args("bb_policy_adam_step_wide", w, exec_mode, params, grads, state, hyper, &a.s);
+    if (rc != BB_OK) return rc;
+    if (!out2 || (((uintptr_t)out2) & 3u))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_adam_step_wide: out2 is NULL or misaligned");
+    a.s.out = out2;
+    if (exec_mode == BB_EXEC_CPU) {
+        bb::host_policy_step_wide(a, false);
+        return BB_OK;
+    }
+    DeviceGuard g(gpu_id);
+    hipError_t e = bb::launch_adam_step_wide(a, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "launch wide Adam step kernel");
+    return BB_OK;
+}
+
+int64_t bb_policy_ppo_step_wide_workspace_bytes(int32_t in_dim, int64_t m)
+{
+    return bb::ppo_step_wide_workspace_bytes(in_dim, m);
+}
+
+int bb_policy_ppo_step_wide(const bb_policy_weights *w, int32_t in_dim, int32_t exec_mode, int32_t gpu_id,
+                            const bb_ppo_batch *batch, const bb_ppo_coef *coef, const bb_policy_params *params,
+                            const bb_policy_params *grads, const bb_adam_state *state, const bb_adam_hyper *hyper,
+                            float *out6, void *workspace, int64_t workspace_bytes, void *stream)
+{
+    if (!bb::pol_wide_width(in_dim))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step_wide: in_dim must be 184, 264, 344 or 424");
+    bb::PolicyStepWideArgs a{};
+    a.in_dim = in_dim;
+    const int rc = policy_step_args("bb_policy_ppo_step_wide", w, exec_mode, params, grads, state, hyper, &a.s);
+    if (rc != BB_OK) return rc;
+    if (!batch || !coef || !out6 || (((uintptr_t)out6) & 3u))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step_wide: batch, coef or out6 is NULL or misaligned");
+    const void *req[] = {batch->obs, batch->actions, batch->log_prob, batch->value, batch->advantages, batch->returns};
+    for (const void *ptr : req) {
+        if (!ptr) return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step_wide: a batch pointer is NULL");
+        if (((uintptr_t)ptr) & 3u) return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step_wide: a misaligned pointer");
+    }
+    if ((((uintptr_t)batch->obs) & 15u) || (((uintptr_t)w->w1) & 15u) || (((uintptr_t)w->w2) & 15u) ||
+        (((uintptr_t)w->head_w) & 15u) || (((uintptr_t)batch->idx) & 7u))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step_wide: obs and the weight matrices must be 16-byte "
+                                        "aligned, idx 8-byte aligned");
+    if (batch->rows <= 0 || batch->m <= 0 || (!batch->idx && batch->m > batch->rows))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step_wide: rows and m must be positive (m <= rows without idx)");
+    bb::PpoGradArgs ga{};
+    ga.w = a.s.w;
+    ga.obs = batch->obs; ga.actions = batch->actions; ga.log_prob = batch->log_prob; ga.value = batch->value;
+    ga.adv = batch->advantages; ga.ret = batch->returns; ga.idx = batch->idx; ga.rows = batch->rows; ga.m = batch->m;
+    ga.clip = coef->clip_coef; ga.vf_coef = coef->vf_coef; ga.ent_coef = coef->ent_coef;
+    a.s.out = out6;
+    if (exec_mode == BB_EXEC_CPU) {
+        // host_ppo_grad_wide's packed head gradient, then its rows into the actor's and the critic's tensors
+        float hw[bb::POL_HEAD * bb::POL_HID], hb[bb::POL_HEAD];
+        float *const *gr = a.s.grad;
+        ga.g = bb::PolicyGrads{gr[0], gr[1], gr[2], gr[3], gr[4], gr[5], gr[6], gr[7], hw, hb};
+        ga.loss4 = out6;
+        bb::host_ppo_grad_wide(ga, in_dim);
+        std::memcpy(gr[8], hw, sizeof(float) * bb::POL_LOGITS * bb::POL_HID);
+        std::memcpy(gr[10], hw + bb::POL_LOGITS * bb::POL_HID, sizeof(float) * bb::POL_HID);
+        std::memcpy(gr[9], hb, sizeof(float) * bb::POL_LOGITS);
+        gr[11][0] = hb[bb::POL_LOGITS];
+        bb::host_policy_step_wide(a, true);
+        return BB_OK;
+    }
+    if (!workspace || (((uintptr_t)workspace) & 15u) ||
+        workspace_bytes < bb::ppo_step_wide_workspace_bytes(in_dim, batch->m))
+        return fail(BB_ERR_INVALID_ARG, "bb_policy_ppo_step_wide: the workspace is NULL, misaligned or smaller than "
+                                        "bb_policy_ppo_step_wide_workspace_bytes(in_dim, m)");
+    DeviceGuard g(gpu_id);
+    hipError_t e = bb::launch_ppo_step_wide(ga, a, workspace, (hipStream_t)stream);
+    if (e != hipSuccess) return hip_fail(e, "launch wide PPO step kernels");
     return BB_OK;
 }
 

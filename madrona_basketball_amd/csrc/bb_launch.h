@@ -227,17 +227,37 @@ hipError_t launch_ppo_grad_partials(const PpoGradArgs &a, hipStream_t s, int *gr
 hipError_t launch_ppo_grad_wide(const PpoGradArgs &a, int in_dim, void *workspace, hipStream_t s);
 void host_ppo_grad_wide(const PpoGradArgs &a, int in_dim);
 int64_t ppo_grad_wide_workspace_bytes(int in_dim, int64_t m);
+// its two passes without the reduce: pass 1's partials [groups][1 880] and pass 2's
+// [groups_w1][32][in_dim] in the workspace (a.g and a.loss4 are not written)
+struct PpoGradWidePartials {
+    const float *partial;
+    int groups;
+    const float *partial_w1;
+    int groups_w1;
+};
+hipError_t launch_ppo_grad_wide_partials(const PpoGradArgs &a, int in_dim, void *workspace, hipStream_t s,
+                                         PpoGradWidePartials *out);
 // Gradient clipping, Adam's step and the weight repack (bb_policy_step.h / bb_policy_step.hip)
 struct PolicyStepArgs;
 hipError_t launch_adam_step(const PolicyStepArgs &a, hipStream_t s);
 hipError_t launch_ppo_step(PpoGradArgs g, PolicyStepArgs a, void *workspace, hipStream_t s);
 void host_policy_step(const PolicyStepArgs &a, bool fused);
 int64_t ppo_step_workspace_bytes(int64_t m);
+// The same at 184, 264, 344, 424 inputs (bb_policy_step_wide.h / bb_policy_step_wide.hip)
+struct PolicyStepWideArgs;
+hipError_t launch_adam_step_wide(const PolicyStepWideArgs &a, hipStream_t s);
+hipError_t launch_ppo_step_wide(const PpoGradArgs &g, PolicyStepWideArgs a, void *workspace, hipStream_t s);
+void host_policy_step_wide(const PolicyStepWideArgs &a, bool fused);
+int64_t ppo_step_wide_workspace_bytes(int in_dim, int64_t m);
 // GAE, normaliser updates and advantage normalisation (bb_advantages.h / bb_advantages.hip)
 struct AdvArgs;
 hipError_t launch_advantages(const AdvArgs &a, hipStream_t s);
-void host_advantages(const AdvArgs &a);
+hipError_t launch_adv_norm(const AdvArgs &a, hipStream_t s);  // k_adv_norm, from the scalars at a.ws
+void host_advantages(const AdvArgs &a, int in_dim = 128);     // obs [steps][worlds][in_dim], a.on of in_dim statistics
 int64_t advantages_workspace_bytes(int32_t steps, int64_t worlds);
+// The same at 184, 264, 344, 424 inputs (bb_advantages_wide.hip)
+hipError_t launch_advantages_wide(const AdvArgs &a, int in_dim, hipStream_t s);
+int64_t advantages_wide_workspace_bytes(int in_dim, int32_t steps, int64_t worlds);
 hipError_t launch_record(const RecordArgs &a, int64_t world0, int32_t count, uint32_t *dst, hipStream_t s);
 void host_record(const RecordArgs &a, int64_t world0, int32_t count, uint32_t *dst);
 // diagnostics: the step's scalar math on the device (bb_diag_math)

@@ -417,7 +417,9 @@ static hipError_t launch_ppo_grad_wide_t(const PpoGradWideArgs &aw, const PpoGra
     return hipGetLastError();
 }
 
-hipError_t launch_ppo_grad_wide(const PpoGradArgs &a, int in_dim, void *workspace, hipStream_t s)
+// Passes 1 and 2 alone: where their partials lie in the workspace, and how many.
+hipError_t launch_ppo_grad_wide_partials(const PpoGradArgs &a, int in_dim, void *workspace, hipStream_t s,
+                                         PpoGradWidePartials *out)
 {
     if (!pol_wide_width(in_dim) || a.m <= 0) return hipErrorInvalidValue;
     const PpoGradWideGrid gr = ppo_grad_wide_grid(in_dim, a.m);
@@ -426,17 +428,23 @@ hipError_t launch_ppo_grad_wide(const PpoGradArgs &a, int in_dim, void *workspac
     aw.dz1 = (float *)workspace;
     aw.g.partial = aw.dz1 + wide_dz1_floats(a.m);
     aw.partial_w1 = aw.g.partial + (int64_t)gr.groups * PGW_SMALL;
-    hipError_t e;
+    *out = PpoGradWidePartials{aw.g.partial, gr.groups, aw.partial_w1, gr.groups_w1};
     switch (in_dim) {
-    case 184: e = launch_ppo_grad_wide_t<184>(aw, gr, s); break;
-    case 264: e = launch_ppo_grad_wide_t<264>(aw, gr, s); break;
-    case 344: e = launch_ppo_grad_wide_t<344>(aw, gr, s); break;
-    default: e = launch_ppo_grad_wide_t<424>(aw, gr, s); break;
+    case 184: return launch_ppo_grad_wide_t<184>(aw, gr, s);
+    case 264: return launch_ppo_grad_wide_t<264>(aw, gr, s);
+    case 344: return launch_ppo_grad_wide_t<344>(aw, gr, s);
+    default: return launch_ppo_grad_wide_t<424>(aw, gr, s);
     }
+}
+
+hipError_t launch_ppo_grad_wide(const PpoGradArgs &a, int in_dim, void *workspace, hipStream_t s)
+{
+    PpoGradWidePartials pt;
+    const hipError_t e = launch_ppo_grad_wide_partials(a, in_dim, workspace, s, &pt);
     if (e != hipSuccess) return e;
     const int w1_floats = 32 * in_dim, items = w1_floats + PGW_SMALL + PG_HEAD_PAD;
-    hipLaunchKernelGGL(k_ppo_grad_wide_reduce, dim3((items + 63) / 64), dim3(64, 4), 0, s, aw.partial_w1, gr.groups_w1,
-                       aw.g.partial, gr.groups, w1_floats, a.g, a.loss4);
+    hipLaunchKernelGGL(k_ppo_grad_wide_reduce, dim3((items + 63) / 64), dim3(64, 4), 0, s, pt.partial_w1, pt.groups_w1,
+                       pt.partial, pt.groups, w1_floats, a.g, a.loss4);
     return hipGetLastError();
 }
 

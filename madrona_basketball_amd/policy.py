@@ -7,8 +7,10 @@ action tensor -- the `actions, log_probs, values = agent(obs)` +
 `actions[:, i] = a` pair of scripts/ppo.py:67 / scripts/env.py:147 without a
 round trip through torch.  The wide networks also have the minibatch loss and
 gradient in one call (FusedPolicy.ppo_grad_wide, bb_policy_ppo_grad_wide,
-csrc/bb_policy_grad_wide.hip); the rollout, the advantage phase and the fused
-clip + Adam step are 128-wide only.
+csrc/bb_policy_grad_wide.hip), the clip + Adam step behind it
+(optimizer_step / ppo_minibatch / ppo_update, csrc/bb_policy_step_wide.hip) and
+the advantage phase (compute_advantages, csrc/bb_advantages_wide.hip); only
+the fused rollout is 128-wide only.
 
 FusedPolicy.from_agent(agent) snapshots the weights of any torch module with
 the reference Agent's layout (obs_norm.mean/var, backbone Linear/LayerNorm,
@@ -105,11 +107,14 @@ class AdamState:
     for FusedPolicy.optimizer_step / ppo_minibatch / ppo_update: exp_avg and
     exp_avg_sq float32 [5972] in the gradient's packed order (w1 b1 ln1_w ln1_b
     w2 b2 ln2_w ln2_b actor.w critic.w actor.b critic.b), step int64 [1], and
-    the kernels' ticket int32 [1] (0 between calls)."""
+    the kernels' ticket int32 [1] (0 between calls).  in_dim: the policy's
+    input width; a wider first layer has 32 (in_dim - 128) more elements (w1
+    first, every later offset that much further on)."""
 
-    def __init__(self, device=None):
-        self.exp_avg = torch.zeros(PARAMS, dtype=torch.float32, device=device)
-        self.exp_avg_sq = torch.zeros(PARAMS, dtype=torch.float32, device=device)
+    def __init__(self, device=None, *, in_dim: int = IN):
+        n = PARAMS + HID * (int(in_dim) - IN)
+        self.exp_avg = torch.zeros(n, dtype=torch.float32, device=device)
+        self.exp_avg_sq = torch.zeros(n, dtype=torch.float32, device=device)
         self.step = torch.zeros(1, dtype=torch.int64, device=device)
         self.ticket = torch.zeros(1, dtype=torch.int32, device=device)
 
@@ -240,7 +245,8 @@ class FusedPolicy:
     def _require_128(self, what: str) -> None:
         if self.in_dim != IN:
             raise ValueError(f"{what} is built for the 128-wide configuration (the 2-agent game); this policy has "
-                             f"{self.in_dim} inputs: inference only (forward_into, act, act_all)")
+                             f"{self.in_dim} inputs (ppo_grad_wide, optimizer_step, ppo_minibatch, ppo_update and "
+                             "compute_advantages serve it)")
 
     # ------------------------------------------------------------- PPO update
     def ppo_grad(self, obs: torch.Tensor, actions: torch.Tensor, log_prob: torch.Tensor, value: torch.Tensor,
@@ -292,12 +298,9 @@ class FusedPolicy:
         [R, in_dim] -- the rows `idx` gathered by the kernels, the gradient left in
         .grad of the agent's 12 parameters (backbone[0].weight.grad is [32, in_dim]),
         head_grad kept, float32 [4] returned on the device, no host
-        synchronisation.  It is the one fused piece of the wide update; a training
-        step at these widths is
-            ppo_grad_wide(...); clip_grad_norm_(agent.parameters(), c);
-            optimizer.step(); refresh()
-        with torch's own clipping and Adam (optimizer_step, ppo_minibatch,
-        ppo_update, compute_advantages and rollout remain 128-wide)."""
+        synchronisation.  optimizer_step(state) takes the step from these
+        gradients; ppo_minibatch / ppo_update run both without the reduce in
+        between (only rollout remains 128-wide)."""
         if self.in_dim == IN:
             raise ValueError("ppo_grad_wide serves the 184, 264, 344 and 424-input policies; this one has 128 inputs: "
                              "use ppo_grad")
@@ -375,7 +378,11 @@ class FusedPolicy:
     def _step_args(self, state: "AdamState", lr, max_grad_norm, betas, eps, make_grads: bool):
         if not isinstance(state, AdamState) or state.exp_avg.device != self.device:
             raise ValueError("state must be an AdamState on the policy's device")
-        ps = self._params(make_grads)
+        n = PARAMS + HID * (self.in_dim - IN)
+        if state.exp_avg.numel() != n or state.exp_avg_sq.numel() != n:
+            raise ValueError(f"a {self.in_dim}-input policy needs AdamState(device, in_dim={self.in_dim}): {n} "
+                             "elements")
+        ps = self._params(make_grads, self.in_dim)
         if any(not p.is_contiguous() for p in ps):
             raise ValueError("the agent's parameters must be contiguous")
         return (_lib.PolicyParams(*[p.data_ptr() for p in ps]), _lib.PolicyParams(*[p.grad.data_ptr() for p in ps]),
@@ -393,13 +400,15 @@ class FusedPolicy:
         amsgrad), and the new parameters are stored into the packed weights too
         (the observation statistics are not: refresh() after compute_advantages
         as before).  Returns float32 [2] on the device: the gradient norm before
-        clipping and the clip factor (no host synchronisation)."""
-        self._require_128("optimizer_step")
+        clipping and the clip factor (no host synchronisation).  At 184 to 424
+        inputs bb_policy_adam_step_wide, with AdamState(device, in_dim=...)."""
         params, grads, st, hyper = self._step_args(state, lr, max_grad_norm, betas, eps, False)
-        dev = self.device
+        dev, lib = self.device, _lib.load()
         out2 = torch.empty((2,), dtype=torch.float32, device=dev)
-        _lib.check(_lib.load().bb_policy_adam_step(
-            ctypes.byref(self._w), int(ExecMode.CUDA if dev.type == "cuda" else ExecMode.CPU),
+        wide = self.in_dim != IN
+        entry, width = (lib.bb_policy_adam_step_wide, (self.in_dim,)) if wide else (lib.bb_policy_adam_step, ())
+        _lib.check(entry(
+            ctypes.byref(self._w), *width, int(ExecMode.CUDA if dev.type == "cuda" else ExecMode.CPU),
             dev.index if dev.index is not None else -1, ctypes.byref(params), ctypes.byref(grads), ctypes.byref(st),
             ctypes.byref(hyper), ctypes.c_void_p(out2.data_ptr()), self._stream()), "policy_adam_step")
         return out2
@@ -414,19 +423,22 @@ class FusedPolicy:
         (bb_policy_ppo_step) with no torch op between them -- the bits of
         ppo_grad() followed by optimizer_step().  Returns float32 [6] on the
         device: loss, pg_loss, c_loss, entropy, gradient norm before clipping,
-        clip factor."""
-        self._require_128("ppo_minibatch")
-        batch, m = self._ppo_args(obs, actions, log_prob, value, advantages, returns, idx)
+        clip factor.  At 184 to 424 inputs bb_policy_ppo_step_wide: the bits of
+        ppo_grad_wide() followed by optimizer_step()."""
+        wide = self.in_dim != IN
+        batch, m = self._ppo_args(obs, actions, log_prob, value, advantages, returns, idx, self.in_dim)
         params, grads, st, hyper = self._step_args(state, lr, max_grad_norm, betas, eps, True)
         dev, lib = self.device, _lib.load()
         cuda = dev.type == "cuda"
-        need = lib.bb_policy_ppo_step_workspace_bytes(m) if cuda else 0
+        entry, width = (lib.bb_policy_ppo_step_wide, (self.in_dim,)) if wide else (lib.bb_policy_ppo_step, ())
+        query = lib.bb_policy_ppo_step_wide_workspace_bytes if wide else lib.bb_policy_ppo_step_workspace_bytes
+        need = query(*width, m) if cuda else 0
         if getattr(self, "_ppo_ws", None) is None or self._ppo_ws.numel() * 4 < need:
             self._ppo_ws = torch.empty((max(need, 4) // 4,), dtype=torch.float32, device=dev)
         out6 = torch.empty((6,), dtype=torch.float32, device=dev)
         coef = _lib.PpoCoef(float(clip_coef), float(vf_coef), float(ent_coef))
-        _lib.check(lib.bb_policy_ppo_step(
-            ctypes.byref(self._w), int(ExecMode.CUDA if cuda else ExecMode.CPU),
+        _lib.check(entry(
+            ctypes.byref(self._w), *width, int(ExecMode.CUDA if cuda else ExecMode.CPU),
             dev.index if dev.index is not None else -1, ctypes.byref(batch), ctypes.byref(coef), ctypes.byref(params),
             ctypes.byref(grads), ctypes.byref(st), ctypes.byref(hyper), ctypes.c_void_p(out6.data_ptr()),
             ctypes.c_void_p(self._ppo_ws.data_ptr() if cuda else None), need, self._stream()), "policy_ppo_step")
@@ -441,7 +453,6 @@ class FusedPolicy:
         R // num_minibatches rows at range(0, R, minibatch_size) -- a short last
         one when R is not divisible, as ppo.py:188 has it -- each one
         ppo_minibatch(**kw).  Returns float32 [steps, 6], one row per minibatch."""
-        self._require_128("ppo_update")
         rows = obs.shape[0]
         mb = rows // int(num_minibatches)
         if mb < 1:
@@ -461,7 +472,8 @@ class FusedPolicy:
     def compute_advantages(self, buffers: dict, advantages: torch.Tensor, returns: torch.Tensor, value_norm,
                            obs_norm=None, gamma: float = 0.998, gae_lambda: float = 0.95) -> torch.Tensor:
         """compute_advantages (scripts/ppo.py:144-177) on the device,
-        bb_policy_advantages: from the buffers rollout() filled (obs [K, W, 128],
+        bb_policy_advantages (at 184 to 424 inputs bb_policy_advantages_wide): from
+        the buffers of a rollout (obs [K, W, in_dim],
         value / reward / done [K, W], next_value [W]) the GAE recursion on the
         un-normalised values (agent.py:31-34 with clamp 5; the last step's
         non-terminal flag is 1 - done[K-1], as ppo.py:157 has it), then
@@ -470,7 +482,7 @@ class FusedPolicy:
         buffers updated in place), then advantages [K, W] = (A - mean) / (std +
         1e-8) and returns [K, W] = the updated value_norm's clamped normalisation
         of A + values.  value_norm / obs_norm: any objects with float64 tensors
-        mean [dim], var [dim], count [] on the policy's device (dim 1 / 128; a
+        mean [dim], var [dim], count [] on the policy's device (dim 1 / in_dim; a
         RunningMeanStd, a RunningStats); obs_norm=None: the agent's own.
         buffers["value"] is left as it is: ppo.py:175's `values[:] = ...` writes
         to a temporary, and ppo_grad() takes the policy's own normalised values.
@@ -479,12 +491,12 @@ class FusedPolicy:
         tensor on the device: mean and unbiased std of A before normalisation,
         value_norm's new mean and var (no host synchronisation; torch's current
         stream)."""
-        self._require_128("compute_advantages")
-        dev, f32, f64 = self.device, torch.float32, torch.float64
+        dev, f32, f64, width = self.device, torch.float32, torch.float64, self.in_dim
         obs = buffers.get("obs")
-        if (obs is None or obs.dim() != 3 or obs.shape[2] != IN or obs.dtype != f32 or not obs.is_contiguous()
+        if (obs is None or obs.dim() != 3 or obs.shape[2] != width or obs.dtype != f32 or not obs.is_contiguous()
                 or obs.device != dev):
-            raise ValueError("buffers['obs'] must be a contiguous float32 [K, W, 128] tensor on the policy's device")
+            raise ValueError(f"buffers['obs'] must be a contiguous float32 [K, W, {width}] tensor on the policy's "
+                             "device")
         K, W = obs.shape[0], obs.shape[1]
         if K * W < 2:
             raise ValueError("compute_advantages needs at least 2 rows (the unbiased variance of one is undefined)")
@@ -499,7 +511,7 @@ class FusedPolicy:
         if obs_norm is None:
             obs_norm = self.agent.obs_norm
         stats = []
-        for name, norm, dim in (("value_norm", value_norm, 1), ("obs_norm", obs_norm, IN)):
+        for name, norm, dim in (("value_norm", value_norm, 1), ("obs_norm", obs_norm, width)):
             for field, shape in (("mean", (dim,)), ("var", (dim,)), ("count", ())):
                 t = getattr(norm, field, None)
                 if (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != f64
@@ -508,14 +520,18 @@ class FusedPolicy:
             stats.append(_lib.RunningStatsPtrs(norm.mean.data_ptr(), norm.var.data_ptr(), norm.count.data_ptr()))
         lib = _lib.load()
         cuda = dev.type == "cuda"
-        need = lib.bb_policy_advantages_workspace_bytes(K, W) if cuda else 0
+        wide = () if width == IN else (width,)
+        entry = lib.bb_policy_advantages if width == IN else lib.bb_policy_advantages_wide
+        query = (lib.bb_policy_advantages_workspace_bytes if width == IN
+                 else lib.bb_policy_advantages_wide_workspace_bytes)
+        need = query(*wide, K, W) if cuda else 0
         if getattr(self, "_adv_ws", None) is None or self._adv_ws.numel() * 8 < need:
             self._adv_ws = torch.empty((max(need, 8) // 8,), dtype=f64, device=dev)
         out4 = torch.empty((4,), dtype=f32, device=dev)
         batch = _lib.AdvBatch(obs.data_ptr(), named["value"].data_ptr(), named["reward"].data_ptr(),
                               named["done"].data_ptr(), nv.data_ptr(), advantages.data_ptr(), returns.data_ptr(), K, W)
-        _lib.check(lib.bb_policy_advantages(
-            int(ExecMode.CUDA if cuda else ExecMode.CPU), dev.index if dev.index is not None else -1,
+        _lib.check(entry(
+            *wide, int(ExecMode.CUDA if cuda else ExecMode.CPU), dev.index if dev.index is not None else -1,
             ctypes.byref(batch), ctypes.byref(stats[0]), ctypes.byref(stats[1]), float(gamma), float(gae_lambda),
             ctypes.c_void_p(out4.data_ptr()), ctypes.c_void_p(self._adv_ws.data_ptr() if cuda else None), need,
             self._stream()), "policy_advantages")
